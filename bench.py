@@ -1,7 +1,12 @@
 """Headline benchmark: posterior samples/sec of DPS on CelebA-HQ-256 (BASELINE.json).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's samples with
+``--dump-outputs DIR`` (inputs and noise are seeded: the same arguments give the same
+inputs in every run) and prints one JSON line.  ``--full`` adds the legs the headline
+figure does not need (cpu_baseline, collective: below).
 
 Without a launcher, ``--gpus N`` (N > 1) starts its N ranks itself (a child
 torch.distributed.run on 127.0.0.1) and exits with its status.
@@ -31,8 +36,12 @@ Also reported:
                 bytes per launch / mean launch time, against the
                 8 TB/s HBM peak; traffic = PMC-measured HBM bytes per launch
                 (profiles/pmc_traffic.json, separate rocprofv3 --pmc passes)
+
+With ``--full`` only:
   cpu_baseline  oracle/dps_loop.py (torch-CPU restatement of dps.py) with the
                 same UNet, timed on this host's cores for a bounded sample
+  collective    the x-hat all-gather that ends a sharded solve, timed after the
+                steps, and solve_rate_incl_gather
 """
 
 from __future__ import annotations
@@ -84,8 +93,17 @@ def parse():
     p.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32",
                    help="the prior's dtype (fp32: the headline, the reference's run_dps.py:14; bf16: the "
                         "reference's bf16 precision on the bf16 NHWC kernels, behind the fp32 sampler loop)")
-    p.add_argument("--cpu-seconds", type=float, default=15.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU baseline "
+                        "(cpu_baseline) and the x-hat all-gather that ends a sharded solve "
+                        "(collective, solve_rate_incl_gather)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the samples x the last timed step returned "
+                        "as DIR/x.npy (float32; DIR/x_rank<r>.npy with more than one rank; a "
+                        "fixed seeded sample of the elements above 60 MB in all)")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU baseline out")
     return p.parse_args()
 
 
@@ -190,6 +208,30 @@ def measure_gather(x: torch.Tensor, reps: int = 3) -> dict:
         raise SystemExit(f"rank {rank}: its slice of the gathered x differs from its shard")
     return dict(rec, gather_ms=round(min(times[1:]), 4), first_gather_ms=round(times[0], 4),
                 gathered_shape=list(full.shape), own_slice_checked=True)
+
+
+DUMP_BYTES = 60 * 10**6  # all ranks' files together stay under 64 MB
+
+
+def dump_outputs(directory: str, x: torch.Tensor, rank: int, world: int) -> Path:
+    """``--dump-outputs``: what the timed path handed back in its last step (``FusedDPSStep``
+    returns the advanced samples x) as one float32 .npy per rank.  A shard above its share of
+    DUMP_BYTES is written as a 1-D sample of its flattened elements at indices drawn (with
+    replacement) from a generator with a fixed seed, so the same arguments select the same
+    elements in every run and build."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    flat = x.detach().reshape(-1).float()
+    keep = DUMP_BYTES // (4 * world)
+    if flat.numel() > keep:
+        gen = torch.Generator().manual_seed(20260101 + rank)
+        idx = torch.randint(0, flat.numel(), (keep,), generator=gen).sort().values
+        arr = flat[idx.to(flat.device)].cpu().numpy()
+    else:
+        arr = flat.cpu().numpy().reshape(tuple(x.shape))
+    path = out / ("x.npy" if world == 1 else f"x_rank{rank}.npy")
+    np.save(path, np.ascontiguousarray(arr, dtype=np.float32))
+    return path
 
 
 def build_workload(config: str, batch: int, image: int, rank: int, device, dtype=torch.float32):
@@ -483,8 +525,12 @@ def main():
     if not torch.isfinite(x).all():
         raise SystemExit("non-finite samples")
 
-    # the x-hat gather that ends a sharded solve (after the clock: once per solve of 998 steps)
-    collective = measure_gather(x)
+    if args.dump_outputs:
+        log(f"wrote {dump_outputs(args.dump_outputs, x, rank, world)}")
+
+    # --full: the x-hat gather that ends a sharded solve (after the clock: once per solve of
+    # 998 steps)
+    collective = measure_gather(x) if args.full else None
     kern = kern_warm if graph is not None else timer.summary()
     kern_steps = args.warmup if graph is not None else args.steps  # steps the records cover
     nbytes = guidance_bytes(n, m, index_bytes)
@@ -566,24 +612,26 @@ def main():
                                "ddpm-celebahq-256 prior, 1000-step DDPM schedule",
                    "global_batch": args.batch * world, "per_gpu_batch": args.batch,
                    "parallelism": f"sample-batch shards x{world}, no collective inside a step; "
-                                  "one all-gather of x-hat per solve (timed after the steps: "
-                                  "'collective')",
+                                  "one all-gather of x-hat per solve (timed after the steps "
+                                  "with --full: 'collective')",
                    "execution": "hipGraph replay of one captured step" if graph is not None
                    else "eager"},
         # gloo over ranks sharing GPUs (SAMPLERS_AMD_DIST_BACKEND=gloo): a rehearsal of the sharded
         # path and its gather, not a throughput measurement
-        "rehearsal": bool(world > 1 and collective.get("backend") == "gloo"),
+        "rehearsal": bool(world > 1 and dist.get_backend() == "gloo"),
+        # from the timed steps' own dispatch-packet events (no run of their own)
         "roofline": roofline,
         "guidance_roofline": guidance_roofline,
         "guidance_kernels": {k: {"avg_ms": round(v["avg_ms"], 5), "GB/s": round(v["gbs"], 1)}
                              for k, v in rl.items()},
         "groupnorm_recomputed_partials": guard.recomputed,
-        "collective": collective,
-        # a whole 1000-step solve (998 guided steps) of the same shards including its gather
-        "solve_rate_incl_gather": round(args.batch * world * 998 / (
-            998 * elapsed / args.steps + collective["gather_ms"] / 1e3), 3),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if collective is not None:
+        result["collective"] = collective
+        # a whole 1000-step solve (998 guided steps) of the same shards including its gather
+        result["solve_rate_incl_gather"] = round(args.batch * world * 998 / (
+            998 * elapsed / args.steps + collective["gather_ms"] / 1e3), 3)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("timing the CPU baseline ...")
         result["cpu_baseline"] = cpu_baseline(args.image, args.cpu_seconds, args.config,
                                               torch.bfloat16 if bf else torch.float32)

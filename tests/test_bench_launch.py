@@ -62,6 +62,38 @@ def test_bench_help_runs_without_gpu():
     assert out.returncode == 0 and "--gpus" in out.stdout
 
 
+def test_full_and_dump_outputs_options(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path, monkeypatch):
+    """--dump-outputs: the whole shard as float32 when it fits; above the byte budget the same
+    seeded sample of its elements every time, within the budget."""
+    import numpy as np
+    import torch
+
+    x = torch.randn(4, 3, 8, 8, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    path = bench.dump_outputs(str(tmp_path / "d"), x, 0, 1)
+    assert path.name == "x.npy"
+    a = np.load(path)
+    assert a.dtype == np.float32 and a.shape == (4, 3, 8, 8)
+    assert np.array_equal(a, x.float().numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 800)
+    p1 = bench.dump_outputs(str(tmp_path / "a"), x, 1, 2)
+    p2 = bench.dump_outputs(str(tmp_path / "b"), x, 1, 2)
+    assert p1.name == "x_rank1.npy"
+    s1, s2 = np.load(p1), np.load(p2)
+    assert s1.dtype == np.float32 and s1.shape == (100,) and s1.nbytes * 2 <= 800
+    assert np.array_equal(s1, s2)
+    assert np.isin(s1, x.float().numpy().ravel()).all()
+
+
 def _gather_worker(rank, world, port, out_path):
     import os
 

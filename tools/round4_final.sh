@@ -15,7 +15,7 @@ mkdir -p $O
 cd $R
 step() { local t=$1 log=$2; shift 2; echo "[final] $log"; timeout -k 10 $t "$@" > $O/$log 2>&1; local rc=$?; tail -1 $O/$log | cut -c1-160; [ $rc -eq 0 ] || { echo "[final] $log failed rc=$rc"; tail -5 $O/$log; exit $rc; }; }
 if [ "$PART" = benches ]; then
-  step 300 bench_inpaint.log python -u bench.py
+  step 300 bench_inpaint.log python -u bench.py --full
   step 200 bench_blur.log python -u bench.py --config blur --no-cpu-baseline
   step 200 bench_inpaint_512_b16.log python -u bench.py --image 512 --batch 16 --no-cpu-baseline
   step 300 bench_inpaint_512_b24.log python -u bench.py --image 512 --batch 24 --steps 3 --no-cpu-baseline
@@ -24,7 +24,7 @@ if [ "$PART" = benches ]; then
   step 400 bench_psld.log python -u tools/bench_psld.py --cpu-baseline
   step 400 bench_psld_cfg.log python -u tools/bench_psld.py --cfg --cpu-baseline
   step 400 bench_resample.log python -u tools/bench_resample.py --cpu-baseline
-  step 300 bench_gloo2.log env SAMPLERS_AMD_DIST_BACKEND=gloo python -u bench.py --gpus 2 --batch 16 --steps 3 --warmup 1 --no-cpu-baseline
+  step 300 bench_gloo2.log env SAMPLERS_AMD_DIST_BACKEND=gloo python -u bench.py --full --gpus 2 --batch 16 --steps 3 --warmup 1 --no-cpu-baseline
 elif [ "$PART" = pmc ]; then
   cd /tmp && export TMPDIR=/tmp
   for cfg in "inpaint:--config inpaint" "blur:--config blur" "inpaint512:--image 512 --batch 16"; do

@@ -17,15 +17,15 @@ mkdir -p $O
 cd $R
 step() { local t=$1 log=$2; shift 2; echo "[final] $log"; timeout -k 10 $t "$@" > $O/$log 2>&1; local rc=$?; tail -1 $O/$log | cut -c1-160; [ $rc -eq 0 ] || { echo "[final] $log failed rc=$rc"; tail -5 $O/$log; exit $rc; }; }
 if [ "$PART" = benches ]; then
-  step 300 bench_inpaint.log python -u bench.py
+  step 300 bench_inpaint.log python -u bench.py --full
   step 200 bench_blur.log python -u bench.py --config blur --no-cpu-baseline
   step 200 bench_inpaint_512_b16.log python -u bench.py --image 512 --batch 16 --no-cpu-baseline
   step 300 bench_inpaint_512_b24.log python -u bench.py --image 512 --batch 24 --steps 3 --no-cpu-baseline
   step 200 bench_identity_b1.log python -u bench.py --config identity --batch 1 --steps 20 --warmup 3 --no-cpu-baseline
   step 200 bench_identity_b1_graph.log python -u bench.py --config identity --batch 1 --steps 20 --warmup 3 --no-cpu-baseline --graph
   step 300 bench_call_b1.log python -u tools/bench_call.py --batch 1 --steps 1000
-  step 300 bench_gloo2.log env SAMPLERS_AMD_DIST_BACKEND=gloo python -u bench.py --gpus 2 --batch 16 --steps 3 --warmup 1 --no-cpu-baseline
-  step 300 bench_gloo8_blur.log env SAMPLERS_AMD_DIST_BACKEND=gloo python -u bench.py --config blur --gpus 8 --batch 2 --steps 3 --warmup 1 --no-cpu-baseline
+  step 300 bench_gloo2.log env SAMPLERS_AMD_DIST_BACKEND=gloo python -u bench.py --full --gpus 2 --batch 16 --steps 3 --warmup 1 --no-cpu-baseline
+  step 300 bench_gloo8_blur.log env SAMPLERS_AMD_DIST_BACKEND=gloo python -u bench.py --full --config blur --gpus 8 --batch 2 --steps 3 --warmup 1 --no-cpu-baseline
 elif [ "$PART" = latent ]; then
   step 400 bench_psld.log python -u tools/bench_psld.py --cpu-baseline
   step 400 bench_psld_cfg.log python -u tools/bench_psld.py --cfg --cpu-baseline
