@@ -42,8 +42,12 @@ enum {
     SP_OP_INPAINT = 1,  /* inpainting.py:8-195     y = x.flat[kept]            */
     SP_OP_BLUR = 2,     /* new (BASELINE config 3): depthwise separable Gaussian
                            blur with reflect padding; adjoint = exact transpose */
-    SP_OP_MASK = 3      /* inpainting.py:106-109 (flatten=False): y = x with the
+    SP_OP_MASK = 3,     /* inpainting.py:106-109 (flatten=False): y = x with the
                            masked pixels zeroed; uses keep_bits only, m == n   */
+    SP_OP_SR = 4        /* new: x factor super-resolution, y = the factor x factor
+                           average pooling of every channel plane (factor 2, 4
+                           or 8 dividing height and width, m = n / factor^2);
+                           adjoint = exact transpose, A^+ = factor^2 A^T       */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -58,7 +62,7 @@ typedef struct sp_op {
     const int32_t* word_rank;        /* INPAINT: observed count before word w  */
     const float* taps;               /* BLUR: 2*radius+1 normalised taps       */
     int32_t radius;                  /* BLUR: 1..8                             */
-    int32_t reserved;
+    int32_t factor;                  /* SR: 2, 4 or 8 (0 for the other kinds)  */
 } sp_op;
 
 /* Scalars of one DPS step (all fp32, computed on the host exactly as the
@@ -129,7 +133,10 @@ int64_t sp_debug_violations(int32_t reset, int32_t* first_site);
 int sp_debug_selftest(sp_stream_t stream);
 
 /* Number of per-sample partial sums written by sp_dps_residual for `op`
- * (callers allocate batch * sp_rsq_partials(op) floats). */
+ * (callers allocate batch * sp_rsq_partials(op) floats).  SR: the tiles per sample of its
+ * residual pass.  SP_EINVAL for a descriptor the library rejects (SR: factor not 2 / 4 / 8,
+ * channels * height * width != n, a spatial size not divisible by the factor, or
+ * m * factor^2 != n). */
 int64_t sp_rsq_partials(const sp_op* op);
 
 /* DPS pass 1 — replaces dps.py:99-103 up to the prior's VJP and dps.py:117-118:
@@ -137,7 +144,9 @@ int64_t sp_rsq_partials(const sp_op* op);
  *   r   = y - A(x0)                             (inverse_problem.py:17-18)
  *   v   = A^T(grad_scale * r)  -> v_out         (autograd of noise.log_prob through A)
  *   rsq_partial[b][p] = partial sums of r^2 over sample b (dps.py:117-120).
- * v_out is the cotangent of x0; the caller feeds it to the prior's VJP. */
+ * v_out is the cotangent of x0; the caller feeds it to the prior's VJP.
+ * SR: one pass over the factor x factor blocks, v = (grad_scale / factor^2) * r replicated
+ * over each block; one partial per tile of the pass (sp_rsq_partials). */
 int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
                     int64_t batch, int64_t y_div, const sp_dps_coefs* c,
                     float* v_out, float* rsq_partial, sp_stream_t stream);
@@ -147,7 +156,8 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  *   g   = v/a - (k/a) * w          (w = J_eps^T v from the prior's VJP)
  *   x'  = c_ell*x + c_s*x0 + std*xi + gamma/(sqrt(sum_p rsq_partial[b][p]) + norm_eps) * g
  * v: pass NULL to recompute v from (x, eps, y) (IDENTITY/INPAINT/MASK), else
- *    the buffer written by sp_dps_residual (required for BLUR).
+ *    the buffer written by sp_dps_residual (required for BLUR and SR, which run the
+ *    identity-kind update over it: the Philox element index stays the flat element index).
  * rsq_partial: NULL selects a fixed factor, x' = ... + gamma * g — the PGDM update
  *    (pgdm.py:126-135, gamma = -guidance_weight*sqrt(1-acp_t), v = -2 A^T r) and the
  *    PSLD update (psld.py:144-153, gamma = -1, v = the latent cotangent).
@@ -170,9 +180,11 @@ int sp_predict_x0(const float* x, const float* eps, int64_t count, float a, floa
 int sp_randn(float* out, int64_t batch, int64_t n, uint64_t seed, int64_t step,
              int64_t sample_offset, sp_stream_t stream);
 
-/* y = A x (operators/base.py:91-92; linear.py:141-152; inpainting.py:132-145). */
+/* y = A x (operators/base.py:91-92; linear.py:141-152; inpainting.py:132-145).  SR: the block
+ * means, each block summed in the fixed order documented in csrc/sp_sr.hip. */
 int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_stream_t stream);
-/* x = A^T y (linear.py:154-165; inpainting.py:169-187). */
+/* x = A^T y (linear.py:154-165; inpainting.py:169-187).  SR: y / factor^2 replicated over
+ * each block (exact); the pseudo-inverse is factor^2 times this. */
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
@@ -184,7 +196,7 @@ int sp_residual_grad(const float* y, const float* z, int64_t batch, int64_t m, i
 
 /* ---- latent samplers (PSLD psld.py:118-153, ReSample resample.py:131-228) ---------- */
 
-/* PSLD pixel pass for IDENTITY / INPAINT / MASK (BLUR returns SP_EUNSUPPORTED: the
+/* PSLD pixel pass for IDENTITY / INPAINT / MASK / SR (BLUR returns SP_EUNSUPPORTED: the
  * caller composes it from sp_op_apply / sp_op_adjoint):
  *   r = y - A x0,  x_eff = A^T y + x0 - A^T A x0,  atr = A^T r,
  *   rsq_partial[b][p] = partial sums of r^2 (sp_rsq_partials(op) per sample). */
@@ -196,7 +208,8 @@ int sp_sum_partials(const float* partials, int64_t count, float* out, sp_stream_
  * gives 0, as torch's norm backward).  Gluing-term cotangents of psld.py:138-141. */
 int sp_scaled_combine(const float* a, float alpha, const float* b, float beta, const float* norm_sq,
                       int64_t count, float* out, sp_stream_t stream);
-/* c_x0 = -omega * atr / sqrt(*norm_sq) + (I - A^T A) u   (ata_u = A^T A u, BLUR only). */
+/* c_x0 = -omega * atr / sqrt(*norm_sq) + (I - A^T A) u   (ata_u = A^T A u, BLUR only; SR
+ * computes A^T A u = the block mean of u / factor^2 in the kernel, ata_u may be NULL). */
 int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* ata_u,
                       const float* norm_sq, float omega, int64_t batch, float* out,
                       sp_stream_t stream);
@@ -218,7 +231,7 @@ int sp_adamw_step_until(float* param, const float* grad, float* exp_avg, float* 
                         int64_t count, const sp_adamw_coefs* c, const int32_t* stop,
                         sp_stream_t stream);
 /* One iteration of ReSample's pixel-space hard data consistency (resample_kernels.py:32-54:
- * AdamW(lr=1e-2) on MSELoss(y, A x)) for IDENTITY / INPAINT / MASK in one pass over x:
+ * AdamW(lr=1e-2) on MSELoss(y, A x)) for IDENTITY / INPAINT / MASK / SR in one pass over x:
  *   r = y[b/y_div] - A x,  g = A^T(grad_scale * r)  (grad_scale = -2/M, M = elements of the
  *   MSE mean), AdamW update of x / exp_avg / exp_avg_sq in place, r^2 partials
  *   (sp_rsq_partials(op) per sample) of the loss at x before the update.
@@ -311,7 +324,8 @@ int sp_sched_timestep(const sp_step_rec* sched, const int32_t* cursor, int64_t* 
 /* *cursor += 1 */
 int sp_sched_advance(int32_t* cursor, sp_stream_t stream);
 /* sp_dps_residual / sp_dps_update with the scalars (and the Philox step) read from
- * sched[*cursor] on the device. */
+ * sched[*cursor] on the device; every operator kind of the by-value forms (SR included,
+ * which needs v in the update as there). */
 int sp_dps_residual_sched(const sp_op* op, const float* x, const float* eps, const float* y,
                           int64_t batch, int64_t y_div, const sp_step_rec* sched,
                           const int32_t* cursor, float* v_out, float* rsq_partial,

@@ -17,7 +17,7 @@ LIB_PATH = Path(__file__).resolve().parent / "lib" / "libsamplers_hip.so"
 # the bounds-checked debug build (`make debug`; SAMPLERS_HIP_LIB=DEBUG_LIB_PATH selects it)
 DEBUG_LIB_PATH = Path(__file__).resolve().parent / "lib" / "debug" / "libsamplers_hip.so"
 
-SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK = 0, 1, 2, 3
+SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR = 0, 1, 2, 3, 4
 
 _ERRORS = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported"}
 
@@ -38,7 +38,7 @@ class SpOp(ctypes.Structure):
         ("word_rank", ctypes.c_void_p),
         ("taps", ctypes.c_void_p),
         ("radius", ctypes.c_int32),
-        ("reserved", ctypes.c_int32),
+        ("factor", ctypes.c_int32),
     ]
 
 

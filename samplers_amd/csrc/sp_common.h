@@ -21,7 +21,9 @@ namespace sp {
 // Bounds-checked debug build (`make debug`: -DSP_DEBUG=1, samplers_amd/lib/debug/).
 // SP_DCHECK(cond) states an index / range invariant of a kernel.  In the debug build a
 // violated one is counted in a per-translation-unit device word, with the site of the first
-// (SP_TU << 16 | __LINE__; SP_TU numbers the source files, 0 = this header); the kernel then
+// (SP_TU << 16 | __LINE__; SP_TU numbers the source files: 0 = this header, 1 sp_dps, 2 sp_blur,
+// 3 sp_latent, 4 sp_groupnorm, 5 sp_conv, 6 sp_wino, 7 sp_conv_thin, 8 sp_conv_s2, 9 sp_upsample,
+// 10 sp_attention, 11 sp_gemm_x6, 12 sp_transformer, 13 sp_attention6, 14 sp_bf16, 15 sp_sr); the kernel then
 // goes on unchanged (a check never alters what a kernel reads or writes — the buffer range
 // checks of the release build stay as they are), and sp_debug_violations() reads the counts
 // after a device sync.  The release build compiles the checks away.
@@ -217,6 +219,23 @@ __device__ __forceinline__ void inpaint_lookup(const sp_op& op, int64_t j, uint3
 // Observed bits of elements j..j+3 (MASK operator: m == n, no ranks needed).
 __device__ __forceinline__ uint32_t mask_bits(const sp_op& op, int64_t j) {
     return static_cast<uint32_t>(op.keep_bits[j >> 6] >> (j & 63)) & 0xFu;
+}
+
+// ---------------------------------------------------------------------------
+// Scalar pieces shared by the latent samplers' kernels (sp_latent.hip, sp_sr.hip)
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float inv_norm(const float* norm_sq) {
+    const float nrm = sqrtf(*norm_sq);
+    return nrm > 0.f ? 1.f / nrm : 0.f;  // torch's norm backward is 0 at a zero norm
+}
+
+// torch.optim.AdamW update of one parameter (decoupled weight decay, no amsgrad)
+__device__ __forceinline__ void adamw_1(float& p, float g, float& m, float& v, const sp_adamw_coefs& c) {
+    p = p * c.decay;                                // p *= 1 - lr * weight_decay
+    m = m + (1.f - c.beta1) * (g - m);              // exp_avg.lerp_(g, 1 - beta1)
+    v = v * c.beta2 + (1.f - c.beta2) * g * g;      // exp_avg_sq.mul_(beta2).addcmul_
+    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+    p = p - c.step_size * m / denom;
 }
 
 // ---------------------------------------------------------------------------

@@ -407,6 +407,12 @@ bool valid_op(const sp_op* op) {
             return op->taps && op->radius >= 1 && op->radius <= 8 && op->m == op->n &&
                    (int64_t)op->channels * op->height * op->width == op->n &&
                    op->height > 2 * op->radius && op->width > 2 * op->radius;
+        case SP_OP_SR:
+            return (op->factor == 2 || op->factor == 4 || op->factor == 8) && op->channels > 0 &&
+                   op->height > 0 && op->width > 0 &&
+                   (int64_t)op->channels * op->height * op->width == op->n &&
+                   op->height % op->factor == 0 && op->width % op->factor == 0 &&
+                   op->m * op->factor * op->factor == op->n;
         default: return false;
     }
 }
@@ -420,13 +426,22 @@ int blur_dps_residual(const sp_op* op, const float* x, const float* eps, const f
 int blur_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
 int blur_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
 
+// super-resolution entry points (sp_sr.hip)
+int64_t sr_partials(const sp_op* op);
+int sr_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
+                    int64_t batch, int64_t y_div, float a, float k, float gs,
+                    const sp_step_rec* sched, const int32_t* cursor, float* v, float* partial,
+                    hipStream_t s);
+int sr_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
+int sr_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
+
 }  // namespace sp
 
 using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 101; }
+int sp_version(void) { return 102; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -492,6 +507,7 @@ const char* sp_last_error(void) { return g_err; }
 int64_t sp_rsq_partials(const sp_op* op) {
     if (!valid_op(op)) return SP_EINVAL;
     if (op->kind == SP_OP_BLUR) return blur_partials(op);
+    if (op->kind == SP_OP_SR) return sr_partials(op);
     return tiles_elementwise(op->n);
 }
 
@@ -508,6 +524,9 @@ static int dps_residual_impl(const sp_op* op, const float* x, const float* eps, 
     if (op->kind == SP_OP_BLUR)
         return blur_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched,
                                  cursor, v_out, rsq_partial, s);
+    if (op->kind == SP_OP_SR)
+        return sr_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
+                               v_out, rsq_partial, s);
     const int P = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(P, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
@@ -551,13 +570,14 @@ static int dps_update_impl(const sp_op* op, const float* x, const float* eps, co
     if (!valid_op(op) || !x || !eps || !w || !x_out || batch <= 0 || y_div <= 0 ||
         batch > 65535)
         return SP_EINVAL;
-    if (!v && (op->kind == SP_OP_BLUR || !y)) return SP_EINVAL;
+    if (!v && (op->kind == SP_OP_BLUR || op->kind == SP_OP_SR || !y)) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = static_cast<int>(sp_rsq_partials(op));
     const int Pw = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(Pw, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
-    const int opk = op->kind == SP_OP_BLUR ? SP_OP_IDENTITY : op->kind;  // BLUR reads v
+    // BLUR and SR read v: the identity-kind kernel over it (flat Philox element index)
+    const int opk = (op->kind == SP_OP_BLUR || op->kind == SP_OP_SR) ? SP_OP_IDENTITY : op->kind;
 #define SP_K2(OPK, V, VIN, XIN)                                                            \
     launch_w(TK_DPS_UPDATE, (double)batch, k_dps_update<OPK, V, VIN, XIN>, grid, dim3(kBlock), s, *op, x, eps, y, \
            v, w, rsq_partial, P, xi, seed, step, sample_offset, y_div, c, x_out, sched, cursor)
@@ -688,6 +708,7 @@ int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_str
             return check_launch("sp_op_apply");
         }
         case SP_OP_BLUR: return blur_apply(op, x, y, batch, s);
+        case SP_OP_SR: return sr_apply(op, x, y, batch, s);
     }
     return SP_EINVAL;
 }
@@ -719,6 +740,7 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
             return check_launch("sp_op_adjoint");
         }
         case SP_OP_BLUR: return blur_adjoint(op, y, x, batch, s);
+        case SP_OP_SR: return sr_adjoint(op, y, x, batch, s);
     }
     return SP_EINVAL;
 }

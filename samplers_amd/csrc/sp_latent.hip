@@ -21,6 +21,15 @@ namespace sp {
 int64_t tiles_elementwise(int64_t n);
 bool valid_op(const sp_op* op);
 
+// super-resolution entry points (sp_sr.hip)
+int sr_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
+                  float* x_eff, float* atr, float* partial, hipStream_t s);
+int sr_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* norm_sq,
+                      float omega, int64_t batch, float* out, hipStream_t s);
+int sr_pixel_opt(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq, const float* y,
+                 int64_t batch, int64_t y_div, float gs, const sp_adamw_coefs* c,
+                 const int32_t* stop, float* partial, hipStream_t s);
+
 // x_eff and A^T r for the elementwise operators (IDENTITY / INPAINT / MASK)
 template <int OPK, int V>
 __global__ __launch_bounds__(kBlock) void k_psld_pixel(sp_op op, const float* __restrict__ x0,
@@ -74,11 +83,6 @@ __global__ __launch_bounds__(kBlock) void k_sum(const float* __restrict__ p, int
     for (int64_t i = threadIdx.x; i < count; i += kBlock) s += p[i];
     const float t = block_sum(s, red);
     if (threadIdx.x == 0) *out = t;
-}
-
-__device__ __forceinline__ float inv_norm(const float* norm_sq) {
-    const float nrm = sqrtf(*norm_sq);
-    return nrm > 0.f ? 1.f / nrm : 0.f;  // torch's norm backward is 0 at a zero norm
 }
 
 // out = alpha * a + beta / sqrt(*norm_sq) * b   (a may be null)
@@ -184,15 +188,6 @@ __global__ __launch_bounds__(kBlock) void k_stochastic_resample(
         for (int e = 0; e < V; ++e) o[e] = (sigma * sa * pv[e] + oma * xv[e]) / den + z[e] * sd;
         store_v<V>(out + b * n + j, o);
     }
-}
-
-// torch.optim.AdamW update of one parameter (decoupled weight decay, no amsgrad)
-__device__ __forceinline__ void adamw_1(float& p, float g, float& m, float& v, const sp_adamw_coefs& c) {
-    p = p * c.decay;                                // p *= 1 - lr * weight_decay
-    m = m + (1.f - c.beta1) * (g - m);              // exp_avg.lerp_(g, 1 - beta1)
-    v = v * c.beta2 + (1.f - c.beta2) * g * g;      // exp_avg_sq.mul_(beta2).addcmul_
-    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
-    p = p - c.step_size * m / denom;
 }
 
 // torch.optim.AdamW step, in place; a set *stop makes it a no-op (device-side early stop)
@@ -336,6 +331,7 @@ int sp_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batc
         return SP_EINVAL;
     if (op->kind == SP_OP_BLUR) return SP_EUNSUPPORTED;  // composed from apply/adjoint by the caller
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (op->kind == SP_OP_SR) return sr_psld_pixel(op, x0, y, batch, y_div, x_eff, atr, rsq_partial, s);
     const int P = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(P, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
@@ -377,6 +373,7 @@ int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const f
         return SP_EINVAL;
     if (op->kind == SP_OP_BLUR && !ata_u) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (op->kind == SP_OP_SR) return sr_psld_cotangent(op, atr, u, norm_sq, omega, batch, out, s);
     const bool v4 = op->n % 4 == 0;
     const dim3 grid(grid_for(op->n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
 #define SP_CT(OPK, V) \
@@ -453,6 +450,9 @@ int sp_pixel_opt_step(const sp_op* op, float* x, float* exp_avg, float* exp_avg_
         return SP_EINVAL;
     if (op->kind == SP_OP_BLUR) return SP_EUNSUPPORTED;  // composed by the caller
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (op->kind == SP_OP_SR)
+        return sr_pixel_opt(op, x, exp_avg, exp_avg_sq, y, batch, y_div, grad_scale, c, stop,
+                            rsq_partial, s);
     const int P = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(P, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;

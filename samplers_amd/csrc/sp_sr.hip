@@ -1,0 +1,445 @@
+// x s super-resolution (SP_OP_SR): A = s x s average pooling of every channel plane,
+// s in {2, 4, 8}.  A is block-diagonal over the s x s pixel blocks, so A^T, A^T A, A^+ = s^2 A^T
+// and every residual, cotangent and AdamW term the samplers need are local to one block: each
+// entry point that takes an sp_op is ONE pass over x with no halo (the reference has no such
+// operator; semantics in operators/superres.py).
+//
+// Tile body (shared by all kernels below): a thread owns a patch of S rows x PW columns of one
+// plane.  PW = 4 on the vector path (planes with W % 4 == 0: one float4 per patch row, all row
+// loads issued before any arithmetic), so a patch is two blocks (S = 2), exactly one (S = 4) or
+// the left / right half of one (S = 8: the two lanes of a pair exchange their half sums with
+// __shfl_xor, no LDS).  Patches are numbered along the row (column group fastest, then the
+// patch rows of all planes), consecutive lanes take consecutive patches, so one load
+// instruction of a wave covers contiguous bytes of an image row.  W % 4 != 0 can only happen
+// with S = 2 (factors 4 and 8 divide W); those planes take the scalar path PW = S = 2, one
+// thread per low-resolution pixel.
+//
+// Arithmetic: 1 / s^2 is a power of two, so the scaling of A, A^T and A^+ is exact; only the
+// s^2-term block sum rounds, and it is always taken in this order, whatever the path, batch or
+// shard: within a patch row the lane's columns pairwise, (c0 + c1) [+ (c2 + c3)]; the S row
+// sums by a balanced tree, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)); for S = 8 the
+// left half plus the right half (one commutative add, so both lanes hold the same bits).
+// Residual-norm partials: one per tile (block_sum's fixed order), grid = (tiles, batch).
+
+#include <algorithm>
+
+#define SP_TU 15  // debug-build site numbering (sp_common.h SP_DCHECK)
+#include "sp_common.h"
+
+namespace sp {
+
+bool valid_op(const sp_op* op);
+
+template <int S, int PW>
+struct sr_cfg {
+    static_assert((S == 2 || S == 4 || S == 8) && (PW == 4 || (PW == 2 && S == 2)), "patch shape");
+    static constexpr int NY = PW > S ? PW / S : 1;     // low-resolution pixels of a patch
+    static constexpr bool kPair = PW < S;              // two lanes share one block (S = 8)
+    static constexpr int kIter = (PW == 4 && S == 2) ? 2 : 1;  // patches per thread
+    static constexpr int kTile = kBlock * kIter;       // patches per workgroup (even)
+    static constexpr float kInv = 1.f / (S * S);
+};
+
+// where patch p of a sample lies: offset of its first element in the x row, of its first
+// low-resolution pixel in the y row.  p counts (patch row over all planes, column group).
+template <int S, int PW>
+struct sr_patch {
+    int64_t xo, yo;
+    bool own;  // this lane writes / counts the patch's low-resolution pixel(s)
+    __device__ __forceinline__ sr_patch(const sp_op& op, int64_t p) {
+        const int wg = op.width / PW;  // column groups per row
+        const int64_t row = p / wg;    // patch row: plane * (H / S) + row of blocks
+        const int cg = static_cast<int>(p - row * wg);
+        xo = row * S * op.width + cg * PW;
+        yo = row * (op.width / S) + (cg * PW) / S;
+        own = !sr_cfg<S, PW>::kPair || (cg & 1) == 0;
+        SP_DCHECK(xo >= 0 && xo + (int64_t)(S - 1) * op.width + PW <= op.n);
+        SP_DCHECK((yo >= 0 && yo + sr_cfg<S, PW>::NY <= op.m));
+    }
+};
+
+template <int S, int PW, bool NT = false>
+__device__ __forceinline__ void sr_load(const float* __restrict__ base, int64_t xo, int width,
+                                        float (&r)[S][PW]) {
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        if constexpr (PW == 4) {
+            load_v<4, NT>(base + xo + (int64_t)i * width, r[i]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < PW; ++e) r[i][e] = base[xo + (int64_t)i * width + e];
+        }
+    }
+}
+
+template <int S, int PW>
+__device__ __forceinline__ void sr_store(float* __restrict__ base, int64_t xo, int width,
+                                         const float (&r)[S][PW]) {
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        if constexpr (PW == 4) {
+            store_v<4>(base + xo + (int64_t)i * width, r[i]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < PW; ++e) base[xo + (int64_t)i * width + e] = r[i][e];
+        }
+    }
+}
+
+// the patch's NY low-resolution pixels of a y row
+template <int NY>
+__device__ __forceinline__ void sr_load_y(const float* __restrict__ yb, int64_t yo, float (&y)[NY]) {
+    if constexpr (NY == 2) {
+        const float2 t = *reinterpret_cast<const float2*>(yb + yo);  // yo is even (W % 4 == 0)
+        y[0] = t.x, y[1] = t.y;
+    } else {
+        y[0] = yb[yo];
+    }
+}
+
+template <int NY>
+__device__ __forceinline__ void sr_store_y(float* __restrict__ yb, int64_t yo, const float (&y)[NY]) {
+    if constexpr (NY == 2) {
+        *reinterpret_cast<float2*>(yb + yo) = make_float2(y[0], y[1]);
+    } else {
+        yb[yo] = y[0];
+    }
+}
+
+// Block sums of a patch in the fixed order of the file comment.  Every lane of the wave must
+// call it (S = 8 exchanges half sums between the lanes of a pair).
+template <int S, int PW>
+__device__ __forceinline__ void sr_block_sums(const float (&r)[S][PW], float (&sum)[sr_cfg<S, PW>::NY]) {
+    constexpr int NY = sr_cfg<S, PW>::NY;
+#pragma unroll
+    for (int j = 0; j < NY; ++j) {
+        float rows[S];
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            if constexpr (PW == 4 && S >= 4) rows[i] = (r[i][0] + r[i][1]) + (r[i][2] + r[i][3]);
+            else rows[i] = r[i][2 * j] + r[i][2 * j + 1];
+        }
+#pragma unroll
+        for (int w = 1; w < S; w *= 2)
+#pragma unroll
+            for (int i = 0; i < S; i += 2 * w) rows[i] += rows[i + w];
+        sum[j] = rows[0];
+    }
+    if constexpr (sr_cfg<S, PW>::kPair) sum[0] += __shfl_xor(sum[0], 1, 64);
+}
+
+// column e of a patch belongs to low-resolution pixel e / S of the patch (0 when PW <= S)
+template <int S, int PW>
+__device__ __forceinline__ constexpr int sr_pixel_of(int e) { return PW > S ? e / S : 0; }
+
+// y = A x
+template <int S, int PW>
+__global__ __launch_bounds__(kBlock) void k_sr_apply(sp_op op, const float* __restrict__ x,
+                                                     float* __restrict__ y) {
+    using cfg = sr_cfg<S, PW>;
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;  // pairs are in or out together (T and the tile base are even)
+        float r[S][PW] = {};
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        if (in) sr_load<S, PW>(x + b * op.n, pt.xo, op.width, r);
+        float s[cfg::NY];
+        sr_block_sums<S, PW>(r, s);
+#pragma unroll
+        for (int j = 0; j < cfg::NY; ++j) s[j] *= cfg::kInv;
+        if (in && pt.own) sr_store_y<cfg::NY>(y + b * op.m, pt.yo, s);
+    }
+}
+
+// x = scale * (y replicated over its block): scale = 1 / s^2 is A^T
+template <int S, int PW>
+__global__ __launch_bounds__(kBlock) void k_sr_adjoint(sp_op op, const float* __restrict__ y,
+                                                       float scale, float* __restrict__ x) {
+    using cfg = sr_cfg<S, PW>;
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        if (p >= T) continue;
+        const sr_patch<S, PW> pt(op, p);
+        float yv[cfg::NY], r[S][PW];
+        sr_load_y<cfg::NY>(y + b * op.m, pt.yo, yv);
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int e = 0; e < PW; ++e) r[i][e] = scale * yv[sr_pixel_of<S, PW>(e)];
+        sr_store<S, PW>(x + b * op.n, pt.xo, op.width, r);
+    }
+}
+
+// DPS pass 1: x0 = (x - k eps) / a on the block, r = y - mean(x0), v = (gs / s^2) r broadcast,
+// r^2 partial of the tile
+template <int S, int PW>
+__global__ __launch_bounds__(kBlock) void k_sr_dps_residual(sp_op op, const float* __restrict__ x,
+                                                            const float* __restrict__ eps,
+                                                            const float* __restrict__ y, int64_t y_div,
+                                                            float a, float k, float gs,
+                                                            float* __restrict__ v,
+                                                            float* __restrict__ partial, int P,
+                                                            const sp_step_rec* __restrict__ sched,
+                                                            const int32_t* __restrict__ cursor) {
+    using cfg = sr_cfg<S, PW>;
+    __shared__ float red[4];
+    if (sched) {  // device-resident schedule (graph replay): uniform scalar loads
+        const sp_dps_coefs& c = sched[*cursor].c;
+        a = c.a, k = c.k, gs = c.grad_scale;
+    }
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+    const float* yb = y + (b / y_div) * op.m;
+    const float gsi = gs * cfg::kInv;
+    float acc = 0.f;
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        // issue every load of the patch first (memory-level parallelism), then compute
+        float xv[S][PW] = {}, ev[S][PW] = {}, yv[cfg::NY] = {};
+        if (in) {
+            sr_load<S, PW, true>(x + b * op.n, pt.xo, op.width, xv);
+            sr_load<S, PW, true>(eps + b * op.n, pt.xo, op.width, ev);
+            sr_load_y<cfg::NY>(yb, pt.yo, yv);
+        }
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int e = 0; e < PW; ++e) xv[i][e] = (xv[i][e] - k * ev[i][e]) / a;
+        float s[cfg::NY], vv[cfg::NY];
+        sr_block_sums<S, PW>(xv, s);
+#pragma unroll
+        for (int j = 0; j < cfg::NY; ++j) {
+            const float r = yv[j] - s[j] * cfg::kInv;
+            vv[j] = gsi * r;
+            if (in && pt.own) acc += r * r;
+        }
+        if (in) {
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int e = 0; e < PW; ++e) xv[i][e] = vv[sr_pixel_of<S, PW>(e)];
+            sr_store<S, PW>(v + b * op.n, pt.xo, op.width, xv);
+        }
+    }
+    const float t = block_sum(acc, red);
+    SP_DCHECK(static_cast<int>(blockIdx.x) < P);
+    if (threadIdx.x == 0) partial[b * P + blockIdx.x] = t;
+}
+
+// PSLD pixel pass: r = y - A x0, atr = A^T r, x_eff = x0 + atr (= A^T y + x0 - A^T A x0)
+template <int S, int PW>
+__global__ __launch_bounds__(kBlock) void k_sr_psld_pixel(sp_op op, const float* __restrict__ x0,
+                                                          const float* __restrict__ y, int64_t y_div,
+                                                          float* __restrict__ x_eff,
+                                                          float* __restrict__ atr,
+                                                          float* __restrict__ partial, int P) {
+    using cfg = sr_cfg<S, PW>;
+    __shared__ float red[4];
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+    const float* yb = y + (b / y_div) * op.m;
+    float acc = 0.f;
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        float xv[S][PW] = {}, yv[cfg::NY] = {};
+        if (in) {
+            sr_load<S, PW>(x0 + b * op.n, pt.xo, op.width, xv);
+            sr_load_y<cfg::NY>(yb, pt.yo, yv);
+        }
+        float s[cfg::NY], ar[cfg::NY];
+        sr_block_sums<S, PW>(xv, s);
+#pragma unroll
+        for (int j = 0; j < cfg::NY; ++j) {
+            const float r = yv[j] - s[j] * cfg::kInv;
+            ar[j] = r * cfg::kInv;
+            if (in && pt.own) acc += r * r;
+        }
+        if (in) {
+            float av[S][PW];
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int e = 0; e < PW; ++e) {
+                    av[i][e] = ar[sr_pixel_of<S, PW>(e)];
+                    xv[i][e] += av[i][e];
+                }
+            sr_store<S, PW>(atr + b * op.n, pt.xo, op.width, av);
+            sr_store<S, PW>(x_eff + b * op.n, pt.xo, op.width, xv);
+        }
+    }
+    const float t = block_sum(acc, red);
+    SP_DCHECK(static_cast<int>(blockIdx.x) < P);
+    if (threadIdx.x == 0) partial[b * P + blockIdx.x] = t;
+}
+
+// c_x0 = -omega atr / L + (I - A^T A) u, with A^T A u = (block mean of u) / s^2 broadcast
+template <int S, int PW>
+__global__ __launch_bounds__(kBlock) void k_sr_psld_cotangent(sp_op op, const float* __restrict__ atr,
+                                                              const float* __restrict__ u,
+                                                              const float* __restrict__ norm_sq,
+                                                              float omega, float* __restrict__ out) {
+    using cfg = sr_cfg<S, PW>;
+    const float cl = -omega * inv_norm(norm_sq);
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        float uv[S][PW] = {}, av[S][PW] = {};
+        if (in) {
+            sr_load<S, PW>(u + b * op.n, pt.xo, op.width, uv);
+            sr_load<S, PW>(atr + b * op.n, pt.xo, op.width, av);
+        }
+        float s[cfg::NY];
+        sr_block_sums<S, PW>(uv, s);
+        if (in) {
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int e = 0; e < PW; ++e)
+                    uv[i][e] = cl * av[i][e] +
+                               (uv[i][e] - (s[sr_pixel_of<S, PW>(e)] * cfg::kInv) * cfg::kInv);
+            sr_store<S, PW>(out + b * op.n, pt.xo, op.width, uv);
+        }
+    }
+}
+
+// One iteration of ReSample's pixel-space hard data consistency (sp_latent.hip k_pixel_opt):
+// r = y - A x, g = A^T(gs r), AdamW update of x in place, r^2 partial of the loss before the
+// update.  A set *stop makes it a no-op.
+template <int S, int PW>
+__global__ __launch_bounds__(kBlock) void k_sr_pixel_opt(sp_op op, float* __restrict__ x,
+                                                         float* __restrict__ m, float* __restrict__ v,
+                                                         const float* __restrict__ y, int64_t y_div,
+                                                         float gs, sp_adamw_coefs c,
+                                                         const int32_t* __restrict__ stop,
+                                                         float* __restrict__ partial, int P) {
+    using cfg = sr_cfg<S, PW>;
+    __shared__ float red[4];
+    if (stop && *stop) return;
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+    const float* yb = y + (b / y_div) * op.m;
+    const float gsi = gs * cfg::kInv;
+    float acc = 0.f;
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        float xv[S][PW] = {}, mv[S][PW] = {}, vv[S][PW] = {}, yv[cfg::NY] = {};
+        if (in) {
+            sr_load<S, PW>(x + b * op.n, pt.xo, op.width, xv);
+            sr_load<S, PW>(m + b * op.n, pt.xo, op.width, mv);
+            sr_load<S, PW>(v + b * op.n, pt.xo, op.width, vv);
+            sr_load_y<cfg::NY>(yb, pt.yo, yv);
+        }
+        float s[cfg::NY], g[cfg::NY];
+        sr_block_sums<S, PW>(xv, s);
+#pragma unroll
+        for (int j = 0; j < cfg::NY; ++j) {
+            const float r = yv[j] - s[j] * cfg::kInv;
+            g[j] = gsi * r;
+            if (in && pt.own) acc += r * r;
+        }
+        if (in) {
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int e = 0; e < PW; ++e)
+                    adamw_1(xv[i][e], g[sr_pixel_of<S, PW>(e)], mv[i][e], vv[i][e], c);
+            sr_store<S, PW>(x + b * op.n, pt.xo, op.width, xv);
+            sr_store<S, PW>(m + b * op.n, pt.xo, op.width, mv);
+            sr_store<S, PW>(v + b * op.n, pt.xo, op.width, vv);
+        }
+    }
+    const float t = block_sum(acc, red);
+    SP_DCHECK(static_cast<int>(blockIdx.x) < P);
+    if (threadIdx.x == 0) partial[b * P + blockIdx.x] = t;
+}
+
+// ---------------------------------------------------------------------------
+// host side (called from the entry points in sp_dps.hip / sp_latent.hip; `op` is valid)
+// ---------------------------------------------------------------------------
+static inline bool sr_vec(const sp_op* op) { return op->width % 4 == 0; }
+
+// patches per workgroup of the path `op` takes
+static inline int64_t sr_tile(const sp_op* op) {
+    if (!sr_vec(op)) return sr_cfg<2, 2>::kTile;
+    return op->factor == 2 ? sr_cfg<2, 4>::kTile : op->factor == 4 ? sr_cfg<4, 4>::kTile
+                                                                   : sr_cfg<8, 4>::kTile;
+}
+
+// tiles per sample = r^2 partials per sample
+int64_t sr_partials(const sp_op* op) {
+    const int64_t patches = op->n / ((int64_t)op->factor * (sr_vec(op) ? 4 : 2));
+    return (patches + sr_tile(op) - 1) / sr_tile(op);
+}
+
+// KERNEL<S, PW> for the operator's factor and path (W % 4 != 0 implies factor 2)
+#define SR_LAUNCH(KIND, WORK, KERNEL, ...)                                                      \
+    do {                                                                                        \
+        const dim3 grid_(static_cast<unsigned>(sr_partials(op)), static_cast<unsigned>(batch)); \
+        if (!sr_vec(op))                                                                        \
+            launch_w(KIND, WORK, KERNEL<2, 2>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
+        else if (op->factor == 2)                                                               \
+            launch_w(KIND, WORK, KERNEL<2, 4>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
+        else if (op->factor == 4)                                                               \
+            launch_w(KIND, WORK, KERNEL<4, 4>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
+        else                                                                                    \
+            launch_w(KIND, WORK, KERNEL<8, 4>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
+    } while (0)
+
+int sr_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s) {
+    SR_LAUNCH(0, 0.0, k_sr_apply, *op, x, y);
+    return check_launch("sp_op_apply");
+}
+
+int sr_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s) {
+    const float scale = 1.f / static_cast<float>(op->factor * op->factor);
+    SR_LAUNCH(0, 0.0, k_sr_adjoint, *op, y, scale, x);
+    return check_launch("sp_op_adjoint");
+}
+
+int sr_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
+                    int64_t batch, int64_t y_div, float a, float k, float gs,
+                    const sp_step_rec* sched, const int32_t* cursor, float* v, float* partial,
+                    hipStream_t s) {
+    const int P = static_cast<int>(sr_partials(op));
+    SR_LAUNCH(TK_DPS_RESIDUAL, (double)batch, k_sr_dps_residual, *op, x, eps, y, y_div, a, k, gs, v,
+              partial, P, sched, cursor);
+    return check_launch("sp_dps_residual");
+}
+
+int sr_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
+                  float* x_eff, float* atr, float* partial, hipStream_t s) {
+    const int P = static_cast<int>(sr_partials(op));
+    SR_LAUNCH(0, 0.0, k_sr_psld_pixel, *op, x0, y, y_div, x_eff, atr, partial, P);
+    return check_launch("sp_psld_pixel");
+}
+
+int sr_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* norm_sq,
+                      float omega, int64_t batch, float* out, hipStream_t s) {
+    SR_LAUNCH(0, 0.0, k_sr_psld_cotangent, *op, atr, u, norm_sq, omega, out);
+    return check_launch("sp_psld_cotangent");
+}
+
+int sr_pixel_opt(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq, const float* y,
+                 int64_t batch, int64_t y_div, float gs, const sp_adamw_coefs* c,
+                 const int32_t* stop, float* partial, hipStream_t s) {
+    const int P = static_cast<int>(sr_partials(op));
+    SR_LAUNCH(0, 0.0, k_sr_pixel_opt, *op, x, exp_avg, exp_avg_sq, y, y_div, gs, *c, stop, partial, P);
+    return check_launch("sp_pixel_opt_step");
+}
+
+#undef SR_LAUNCH
+
+}  // namespace sp

@@ -12,6 +12,7 @@ from .inpainting import (
     get_mask_side_painting,
 )
 from .linear import GeneralSVDOperator, LinearOperator, SVDOperator
+from .superres import SuperResolutionOperator
 
 __all__ = [
     "Operator",
@@ -26,6 +27,7 @@ __all__ = [
     "SidePaintingOperator",
     "RandomInpaintingOperator",
     "GaussianBlurOperator",
+    "SuperResolutionOperator",
     "get_mask_inpaint_center",
     "get_mask_side_painting",
     "get_mask_random",

@@ -23,6 +23,10 @@ class Operator(torch.nn.Module, ABC):
     """Generic forward model ``A`` (``apply`` mandatory; ``apply_transpose`` and
     ``apply_pseudo_inverse`` optional, raising ``NotImplementedError``)."""
 
+    # c in ∂/∂x̂₀ ‖A⁺y − A⁺A x̂₀‖² = −c·Aᵀ(y − A x̂₀) for natively implemented operators with a
+    # pseudo-inverse (the fused PGDM step): 2 for partial isometries (A⁺ = Aᵀ).
+    pinv_grad_scale: float = 2.0
+
     def __init__(self, x_shape: Shape, device: Device = None) -> None:
         super().__init__()
         self.x_shape = tuple(x_shape)

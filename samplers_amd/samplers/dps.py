@@ -129,8 +129,8 @@ class FusedDPSStep:
         if desc is None:
             raise NotImplementedError(
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
-                "supports IdentityOperator, InpaintingOperator (and subclasses) and "
-                "GaussianBlurOperator"
+                "supports IdentityOperator, InpaintingOperator (and subclasses), "
+                "GaussianBlurOperator and SuperResolutionOperator"
             )
         _hip.require_cuda(observation_rows, "DPSSampler")
         if observation_rows.dtype != torch.float32:
@@ -149,9 +149,10 @@ class FusedDPSStep:
         if mode not in ("dps", "pgdm"):
             raise ValueError(mode)
         self.mode = mode
-        # DPS: d log p/d(Ax) = c r.  PGDM: d/dx0 of ||A^+ y - A^+ A x0||^2 = -2 A^T r for the
-        # partial isometries with a native kernel (A^+ = A^T: identity, inpainting, mask).
-        self.grad_scale = -2.0
+        # DPS: d log p/d(Ax) = c r.  PGDM: d/dx0 of ||A^+ y - A^+ A x0||^2 = -c A^T r with the
+        # operator's pinv_grad_scale c: 2 for the partial isometries (A^+ = A^T: identity,
+        # inpainting, mask), 2 s^2 for x s super-resolution (A^+ = s^2 A^T).
+        self.grad_scale = -float(getattr(op, "pinv_grad_scale", 2.0))
         if mode == "dps":
             gs = getattr(inverse_problem.noise, "grad_scale", None)
             if gs is None:
@@ -168,8 +169,9 @@ class FusedDPSStep:
         # pass 2 re-derives v from (x, eps, y) (default: SURVEY §8d's minimal bytes, 4n + m per
         # sample; with non-temporal loads and 2 float4 groups per thread it is 7 % faster than
         # re-reading pass 1's v, 42.3 vs 45.2 us at B = 64, 256^2) or re-reads v (reuse_v).
-        # Blur always re-reads it (its adjoint needs a halo).
-        self.needs_v = desc.kind == _hip.SP_OP_BLUR or bool(reuse_v)
+        # Blur always re-reads it (its adjoint needs a halo), and so does super-resolution (v is
+        # constant over a block; pass 2 stays the flat identity-kind kernel).
+        self.needs_v = desc.kind in (_hip.SP_OP_BLUR, _hip.SP_OP_SR) or bool(reuse_v)
         self.micro_batch = micro_batch
         self.timer = timer
 

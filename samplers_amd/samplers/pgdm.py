@@ -1,8 +1,9 @@
 """Pseudoinverse-Guided Diffusion Models (mirrors ``/root/reference/samplers/samplers/pgdm.py:18-147``).
 
 Loop body (``pgdm.py:104-135``) on the same two fused HIP passes as DPS:
-pass 1 computes v = ∂/∂x0 ||A⁺y − A⁺A x0||² = −2 Aᵀ(y − A x0) (A⁺ = Aᵀ for the
-identity / inpainting / mask operators, which are partial isometries), the
+pass 1 computes v = ∂/∂x0 ||A⁺y − A⁺A x0||² = −c Aᵀ(y − A x0) with the operator's
+``pinv_grad_scale`` c (2 for the identity / inpainting / mask operators, which are
+partial isometries with A⁺ = Aᵀ; 2·s² for ×s super-resolution, A⁺ = s²·Aᵀ), the
 prior's input-VJP gives w = Jᵀv, and pass 2 writes
 ``ddim_step(x, x0) − guidance_weight·sqrt(1−ᾱ_t)·(v − k w)/a``.
 Operators without ``apply_pseudo_inverse`` raise ``NotImplementedError`` as in
