@@ -17,6 +17,17 @@
  *     launch (the launch error is also readable through sp_last_error()).
  *   - observation row for sample b is b / y_div (y_div = number of
  *     reconstructions sharing one observation, >= 1).
+ *   - alignment.  The elementwise kernels move one float4 per lane when the row length allows.
+ *     Entry points over a flat `count` check their pointers and fall back to scalar access
+ *     (the same arithmetic per element) when count % 4 != 0 or any buffer is not 16-byte aligned:
+ *     sp_scaled_combine, sp_adamw_step, sp_adamw_step_until, sp_predict_x0.  Every other entry
+ *     point over rows of n (or m) elements chooses float4 access from n % 4 == 0 alone and then
+ *     REQUIRES 16-byte aligned row buffers, y included where m == n (rows are n floats apart,
+ *     so the base pointer decides): sp_dps_residual / sp_dps_update and their _sched forms, sp_residual_grad (m),
+ *     sp_randn, sp_op_apply / sp_op_adjoint, sp_psld_pixel, sp_psld_cotangent,
+ *     sp_pixel_opt_step, sp_ddim_eps_step, sp_stochastic_resample.  Packed INPAINT observation
+ *     rows (m elements) and partial-sum buffers are read by scalar loads and need only 4-byte
+ *     alignment.  With n % 4 != 0 all access is scalar and 4-byte alignment suffices.
  */
 #ifndef SAMPLERS_HIP_H
 #define SAMPLERS_HIP_H

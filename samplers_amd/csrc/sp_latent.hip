@@ -99,8 +99,10 @@ __global__ __launch_bounds__(kBlock) void k_scaled_combine(const float* __restri
         if (a) {
             float av[V];
             load_v<V>(a + j, av);
+            // explicit fma: which product is fused must not depend on the instantiation (V = 4 or the
+            // scalar fallback for unaligned pointers), or a pointer's alignment changes the bits
 #pragma unroll
-            for (int e = 0; e < V; ++e) o[e] = alpha * av[e] + cb * bv[e];
+            for (int e = 0; e < V; ++e) o[e] = __builtin_fmaf(alpha, av[e], cb * bv[e]);
         } else {
 #pragma unroll
             for (int e = 0; e < V; ++e) o[e] = cb * bv[e];
@@ -156,10 +158,14 @@ __global__ __launch_bounds__(kBlock) void k_ddim_eps(const float* __restrict__ x
         else philox_normals<V>(seed, step, offset + b, j, z);
 #pragma unroll
         for (int e2 = 0; e2 < V; ++e2) {
-            const float p0 = (xv[e2] - c.sqrt_oma * ev[e2]) / c.sqrt_a;
+            // Every multiply-add is an explicit fma.  Left to the compiler's contraction, which of
+            // the products of x_prev is fused differed between the instantiations (injected noise
+            // or Philox), so the same inputs gave x_prev bits that depended on the noise source.
+            const float p0 = __builtin_fmaf(-c.sqrt_oma, ev[e2], xv[e2]) / c.sqrt_a;
             o1[e2] = p0;
-            o2[e2] = (xv[e2] - c.oma * ev[e2]) / c.sqrt_a;
-            o0[e2] = (c.sqrt_a_prev * p0 + c.dir * ev[e2]) + c.sigma * z[e2];
+            o2[e2] = __builtin_fmaf(-c.oma, ev[e2], xv[e2]) / c.sqrt_a;
+            o0[e2] = __builtin_fmaf(c.sigma, z[e2],
+                                    __builtin_fmaf(c.sqrt_a_prev, p0, c.dir * ev[e2]));
         }
         if (x_prev) store_v<V>(x_prev + b * n + j, o0);
         if (x0) store_v<V>(x0 + b * n + j, o1);
@@ -174,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_stochastic_resample(
     const float* __restrict__ xi, uint64_t seed, int64_t step, int64_t offset, float* __restrict__ out) {
     const int64_t b = blockIdx.y;
     const float oma = 1.f - a_t;
-    const float sa = sqrtf(a_t);
+    const float ssa = sigma * sqrtf(a_t);
     const float den = (sigma + 1.f) - a_t;  // sigma + 1 - a_t, evaluated as the reference does
     const float sd = sqrtf(1.f / (1.f / sigma + 1.f / oma));
     const int64_t stride = (int64_t)gridDim.x * kBlock * V;
@@ -184,8 +190,12 @@ __global__ __launch_bounds__(kBlock) void k_stochastic_resample(
         load_v<V>(xt + b * n + j, xv);
         if constexpr (XI_IN) load_v<V>(xi + b * n + j, z);
         else philox_normals<V>(seed, step, offset + b, j, z);
+        // explicit fma: the compiler's own contraction fused the mean's products in the scalar
+        // kernel's two-element loop body but not in its remainder, so an element's bits depended
+        // on the grid (the batch a sample was sharded into)
 #pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = (sigma * sa * pv[e] + oma * xv[e]) / den + z[e] * sd;
+        for (int e = 0; e < V; ++e)
+            o[e] = __builtin_fmaf(z[e], sd, __builtin_fmaf(ssa, pv[e], oma * xv[e]) / den);
         store_v<V>(out + b * n + j, o);
     }
 }

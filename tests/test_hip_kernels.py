@@ -19,12 +19,21 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _box_mask(shape):
+    """A mask whose 64-bit keep words are each all-kept or all-dropped: the second quarter of
+    the words and the last (possibly partial) word are missing."""
+    n = math.prod(shape)
+    words = (n + 63) // 64
+    w = torch.arange(n) // 64
+    return (((w >= words // 4) & (w < words // 2)) | (w == words - 1)).reshape(shape)
+
+
 def _op_factory(kind, shape, device):
     if kind == "identity":
         return IdentityOperator(shape)
-    if kind in ("inpaint", "mask"):
-        m = get_mask_random(shape, 0.5, seed=3)
-        return InpaintingOperator(shape, m, flatten=(kind == "inpaint")).to(device)
+    if kind in ("inpaint", "mask", "inpaint_box", "mask_box"):
+        m = _box_mask(shape) if kind.endswith("_box") else get_mask_random(shape, 0.5, seed=3)
+        return InpaintingOperator(shape, m, flatten=kind.startswith("inpaint")).to(device)
     if kind == "blur":
         return GaussianBlurOperator(shape, 9, 3.0).to(device)
     raise ValueError(kind)
@@ -34,9 +43,9 @@ def _np_ops(kind, op, shape):
     n = math.prod(shape)
     if kind == "identity":
         return closed_form.identity_ops()
-    if kind == "inpaint":
+    if kind.startswith("inpaint"):
         return closed_form.inpaint_ops(op._kept_indices.cpu().numpy(), n)
-    if kind == "mask":
+    if kind.startswith("mask"):
         return closed_form.mask_ops(~op.mask.cpu().numpy())
     return oblur.blur_ops(shape, oblur.taps(9, 3.0))
 
@@ -92,10 +101,12 @@ def test_blur_forward_adjoint(cuda, shape, ks):
     np.testing.assert_allclose(at.numpy(), oblur.blur_adjoint(s, k).numpy(), rtol=0, atol=2e-5)
 
 
-@pytest.mark.parametrize("kind", ["identity", "inpaint", "mask", "blur"])
+@pytest.mark.parametrize("kind", ["identity", "inpaint", "mask", "blur", "inpaint_box", "mask_box"])
 @pytest.mark.parametrize("shape,batch,ydiv", [((3, 32, 32), 4, 1), ((3, 40, 36), 6, 3),
-                                              ((1, 19, 21), 2, 2)])
+                                              ((1, 19, 21), 2, 2), ((1, 37, 83), 3, 1)])
 def test_fused_dps_passes_match_closed_form(cuda, kind, shape, batch, ydiv):
+    """(1, 37, 83): the scalar (n % 4 != 0) kernels over six tiles, the last short by one, with
+    inpaint ranks carried across tiles; "_box": whole keep words all-kept or all-dropped."""
     torch.manual_seed(0)
     op = _op_factory(kind, shape, cuda)
     apply_np, adjoint_np = _np_ops(kind, op, shape)
@@ -114,19 +125,21 @@ def test_fused_dps_passes_match_closed_form(cuda, kind, shape, batch, ydiv):
     P = lib.sp_rsq_partials(desc)
     assert P > 0
     xd, ed, yd, wd, xid = (t.to(cuda).contiguous() for t in (x, eps, y, w, xi))
-    v = torch.empty_like(xd)
-    part = torch.empty(batch, P, device=cuda)
+    v = torch.full_like(xd, float("nan"))
+    part = torch.full((batch, P), float("nan"), device=cuda)
     _hip.check(lib.sp_dps_residual(desc, xd.data_ptr(), ed.data_ptr(), yd.data_ptr(), batch, ydiv,
                                    coefs, v.data_ptr(), part.data_ptr(), _stream()), "residual")
     v_ref, rsq_ref = closed_form.residual_pass(x.numpy(), eps.numpy(), y.numpy(), ydiv, a, k, gs,
                                                apply_np, adjoint_np)
+    if shape == (1, 37, 83) and kind != "blur":
+        assert P > 1
     scale = np.abs(v_ref).max()
     np.testing.assert_allclose(v.cpu().numpy(), v_ref, rtol=0, atol=2e-5 * scale)
     np.testing.assert_allclose(part.sum(1).cpu().numpy(), rsq_ref, rtol=2e-5)
     out_ref = closed_form.update_pass(x.numpy(), eps.numpy(), v_ref, w.numpy(), rsq_ref, xi.numpy(),
                                       a, k, 0.9, 0.2, 0.1, 0.05)
     for v_in in ([v, None] if kind != "blur" else [v]):
-        out = torch.empty_like(xd)
+        out = torch.full_like(xd, float("nan"))
         _hip.check(lib.sp_dps_update(desc, xd.data_ptr(), ed.data_ptr(), yd.data_ptr(),
                                      None if v_in is None else v_in.data_ptr(), wd.data_ptr(),
                                      part.data_ptr(), xid.data_ptr(), 0, 0, 0, batch, ydiv, coefs,
@@ -157,6 +170,38 @@ def test_update_philox_noise_is_shard_invariant(cuda):
                                      None, w[b0].data_ptr(), part[b0].data_ptr(), None, 77, 9, b0, 3,
                                      1, coefs, halves[b0].data_ptr(), _stream()), "update")
     assert torch.equal(full, halves)
+
+
+@pytest.mark.parametrize("kind", ["identity", "inpaint", "mask"])
+@pytest.mark.parametrize("shape", [(3, 32, 32), (1, 37, 83)])
+@pytest.mark.parametrize("philox_noise", [False, True], ids=["xi", "philox"])
+def test_update_in_place_is_bit_equal_to_out_of_place(cuda, kind, shape, philox_noise):
+    """x_out may alias x (every PSLD step and the graph-captured DPS step update in place):
+    with v recomputed from (x, eps, y) and with v given, the in-place result has the bits of
+    the out-of-place one."""
+    torch.manual_seed(2)
+    op = _op_factory(kind, shape, cuda)
+    lib = _hip.load_library()
+    desc = op.hip_descriptor()
+    b, n, m = 3, math.prod(shape), int(desc.m)
+    x, eps, w, xi, v = (torch.randn(b, n, device=cuda) for _ in range(5))
+    y = torch.randn(b, m, device=cuda)
+    coefs = _hip.SpDpsCoefs(0.3, 0.95, 400.0, 0.9, 0.2, 0.1, 0.05, 1e-9)
+    part = torch.rand(b, lib.sp_rsq_partials(desc), device=cuda) + 0.5
+    for v_in in (None, v):
+        for p_in in (part, None):
+            def run(x_in, out):
+                _hip.check(lib.sp_dps_update(desc, x_in.data_ptr(), eps.data_ptr(), y.data_ptr(),
+                                             None if v_in is None else v_in.data_ptr(), w.data_ptr(),
+                                             None if p_in is None else p_in.data_ptr(),
+                                             None if philox_noise else xi.data_ptr(), 77, 9, 4, b, 1,
+                                             coefs, out.data_ptr(), _stream()), "update")
+                return out
+
+            ref = run(x, torch.full_like(x, float("nan")))
+            assert torch.isfinite(ref).all()
+            xc = x.clone()
+            assert torch.equal(run(xc, xc), ref)
 
 
 def test_predict_x0(cuda):
