@@ -55,10 +55,14 @@ enum {
                            blur with reflect padding; adjoint = exact transpose */
     SP_OP_MASK = 3,     /* inpainting.py:106-109 (flatten=False): y = x with the
                            masked pixels zeroed; uses keep_bits only, m == n   */
-    SP_OP_SR = 4        /* new: x factor super-resolution, y = the factor x factor
+    SP_OP_SR = 4,       /* new: x factor super-resolution, y = the factor x factor
                            average pooling of every channel plane (factor 2, 4
                            or 8 dividing height and width, m = n / factor^2);
                            adjoint = exact transpose, A^+ = factor^2 A^T       */
+    SP_OP_PSF = 5       /* new: depthwise dense 2-D point-spread function of
+                           (2*radius+1)^2 taps (motion blur, defocus, measured
+                           PSFs), correlation with reflect padding; adjoint =
+                           exact transpose; no pseudo-inverse; m == n           */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -71,8 +75,10 @@ typedef struct sp_op {
     const uint64_t* keep_bits;       /* INPAINT: ceil(n/64) words; bit (j%64) of
                                         word j/64 set <=> x[j] observed (= ~mask) */
     const int32_t* word_rank;        /* INPAINT: observed count before word w  */
-    const float* taps;               /* BLUR: 2*radius+1 normalised taps       */
-    int32_t radius;                  /* BLUR: 1..8                             */
+    const float* taps;               /* BLUR: 2*radius+1 normalised taps.  PSF: the
+                                        dense row-major (2*radius+1)^2 taps, used
+                                        as given (any finite values)            */
+    int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30                */
     int32_t factor;                  /* SR: 2, 4 or 8 (0 for the other kinds)  */
 } sp_op;
 
@@ -147,8 +153,15 @@ int sp_debug_selftest(sp_stream_t stream);
  * (callers allocate batch * sp_rsq_partials(op) floats).  SR: the tiles per sample of its
  * residual pass.  SP_EINVAL for a descriptor the library rejects (SR: factor not 2 / 4 / 8,
  * channels * height * width != n, a spatial size not divisible by the factor, or
- * m * factor^2 != n). */
+ * m * factor^2 != n).  PSF: the 32 x 64 tiles per sample of its residual launch; rejected
+ * unless taps != NULL, 1 <= radius <= 30, m == n == channels * height * width and
+ * height, width > 2 * radius. */
 int64_t sp_rsq_partials(const sp_op* op);
+/* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
+ * 0 for every kind but PSF (one pass, no workspace), batch * m for PSF (its residual launch
+ * leaves grad_scale * r there for the adjoint launch).  SP_EINVAL for a rejected descriptor
+ * or batch <= 0.  The library allocates nothing. */
+int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
 
 /* DPS pass 1 — replaces dps.py:99-103 up to the prior's VJP and dps.py:117-118:
  *   x0  = (x - k*eps)/a                         (networks/base.py:41-43)
@@ -161,13 +174,21 @@ int64_t sp_rsq_partials(const sp_op* op);
 int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
                     int64_t batch, int64_t y_div, const sp_dps_coefs* c,
                     float* v_out, float* rsq_partial, sp_stream_t stream);
+/* The same with a workspace (sp_dps_workspace floats; NULL where that is 0, and then exactly
+ * sp_dps_residual).  PSF runs here only (sp_dps_residual / _sched return SP_EUNSUPPORTED for
+ * it), as two launches: `residual` forms x0 while staging its tile, writes
+ * work = grad_scale * (y - A x0) and one |r|^2 partial per tile, `adjoint` gathers
+ * v = A^T work (csrc/sp_psf.hip).  work must not alias any other argument. */
+int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                       int64_t batch, int64_t y_div, const sp_dps_coefs* c,
+                       float* v_out, float* rsq_partial, float* work, sp_stream_t stream);
 
 /* DPS pass 2 — replaces dps.py:106-122 (ddim_step -> sample_bridge_kernel and
  * the guidance correction):
  *   g   = v/a - (k/a) * w          (w = J_eps^T v from the prior's VJP)
  *   x'  = c_ell*x + c_s*x0 + std*xi + gamma/(sqrt(sum_p rsq_partial[b][p]) + norm_eps) * g
  * v: pass NULL to recompute v from (x, eps, y) (IDENTITY/INPAINT/MASK), else
- *    the buffer written by sp_dps_residual (required for BLUR and SR, which run the
+ *    the buffer written by sp_dps_residual (required for BLUR, SR and PSF, which run the
  *    identity-kind update over it: the Philox element index stays the flat element index).
  * rsq_partial: NULL selects a fixed factor, x' = ... + gamma * g — the PGDM update
  *    (pgdm.py:126-135, gamma = -guidance_weight*sqrt(1-acp_t), v = -2 A^T r) and the
@@ -192,10 +213,13 @@ int sp_randn(float* out, int64_t batch, int64_t n, uint64_t seed, int64_t step,
              int64_t sample_offset, sp_stream_t stream);
 
 /* y = A x (operators/base.py:91-92; linear.py:141-152; inpainting.py:132-145).  SR: the block
- * means, each block summed in the fixed order documented in csrc/sp_sr.hip. */
+ * means, each block summed in the fixed order documented in csrc/sp_sr.hip.  PSF: the
+ * reflect-padded correlation, every pixel summed tap row by tap row over the rows' non-zero
+ * spans (csrc/sp_psf.hip). */
 int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_stream_t stream);
 /* x = A^T y (linear.py:154-165; inpainting.py:169-187).  SR: y / factor^2 replicated over
- * each block (exact); the pseudo-inverse is factor^2 times this. */
+ * each block (exact); the pseudo-inverse is factor^2 times this.  PSF: a gather (no atomics):
+ * the zero-extended correlation plus the fold terms of the reflect padding, in a fixed order. */
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
@@ -207,8 +231,8 @@ int sp_residual_grad(const float* y, const float* z, int64_t batch, int64_t m, i
 
 /* ---- latent samplers (PSLD psld.py:118-153, ReSample resample.py:131-228) ---------- */
 
-/* PSLD pixel pass for IDENTITY / INPAINT / MASK / SR (BLUR returns SP_EUNSUPPORTED: the
- * caller composes it from sp_op_apply / sp_op_adjoint):
+/* PSLD pixel pass for IDENTITY / INPAINT / MASK / SR (BLUR and PSF, the kinds with a halo,
+ * return SP_EUNSUPPORTED: the caller composes it from sp_op_apply / sp_op_adjoint):
  *   r = y - A x0,  x_eff = A^T y + x0 - A^T A x0,  atr = A^T r,
  *   rsq_partial[b][p] = partial sums of r^2 (sp_rsq_partials(op) per sample). */
 int sp_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
@@ -219,7 +243,8 @@ int sp_sum_partials(const float* partials, int64_t count, float* out, sp_stream_
  * gives 0, as torch's norm backward).  Gluing-term cotangents of psld.py:138-141. */
 int sp_scaled_combine(const float* a, float alpha, const float* b, float beta, const float* norm_sq,
                       int64_t count, float* out, sp_stream_t stream);
-/* c_x0 = -omega * atr / sqrt(*norm_sq) + (I - A^T A) u   (ata_u = A^T A u, BLUR only; SR
+/* c_x0 = -omega * atr / sqrt(*norm_sq) + (I - A^T A) u   (ata_u = A^T A u, BLUR and PSF only,
+ * required there; SR
  * computes A^T A u = the block mean of u / factor^2 in the kernel, ata_u may be NULL). */
 int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* ata_u,
                       const float* norm_sq, float omega, int64_t batch, float* out,
@@ -246,7 +271,7 @@ int sp_adamw_step_until(float* param, const float* grad, float* exp_avg, float* 
  *   r = y[b/y_div] - A x,  g = A^T(grad_scale * r)  (grad_scale = -2/M, M = elements of the
  *   MSE mean), AdamW update of x / exp_avg / exp_avg_sq in place, r^2 partials
  *   (sp_rsq_partials(op) per sample) of the loss at x before the update.
- * No-op once *stop != 0 (stop may be NULL).  BLUR: SP_EUNSUPPORTED (the caller composes
+ * No-op once *stop != 0 (stop may be NULL).  BLUR and PSF: SP_EUNSUPPORTED (the caller composes
  * sp_op_apply / sp_residual_grad / sp_op_adjoint / sp_adamw_step_until). */
 int sp_pixel_opt_step(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq,
                       const float* y, int64_t batch, int64_t y_div, float grad_scale,
@@ -341,6 +366,12 @@ int sp_dps_residual_sched(const sp_op* op, const float* x, const float* eps, con
                           int64_t batch, int64_t y_div, const sp_step_rec* sched,
                           const int32_t* cursor, float* v_out, float* rsq_partial,
                           sp_stream_t stream);
+/* sp_dps_residual_ws with the scalars read from sched[*cursor] (PSF under graph replay; the
+ * other kinds as sp_dps_residual_sched, work may be NULL). */
+int sp_dps_residual_sched_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                             int64_t batch, int64_t y_div, const sp_step_rec* sched,
+                             const int32_t* cursor, float* v_out, float* rsq_partial,
+                             float* work, sp_stream_t stream);
 int sp_dps_update_sched(const sp_op* op, const float* x, const float* eps, const float* y,
                         const float* v, const float* w, const float* rsq_partial,
                         uint64_t seed, int64_t sample_offset, int64_t batch, int64_t y_div,

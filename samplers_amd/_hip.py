@@ -17,7 +17,10 @@ LIB_PATH = Path(__file__).resolve().parent / "lib" / "libsamplers_hip.so"
 # the bounds-checked debug build (`make debug`; SAMPLERS_HIP_LIB=DEBUG_LIB_PATH selects it)
 DEBUG_LIB_PATH = Path(__file__).resolve().parent / "lib" / "debug" / "libsamplers_hip.so"
 
-SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR = 0, 1, 2, 3, 4
+SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR, SP_OP_PSF = 0, 1, 2, 3, 4, 5
+# kinds whose adjoint needs a halo: no fused PSLD / pixel-optimisation pass, the samplers compose
+# them from sp_op_apply / sp_op_adjoint
+HALO_KINDS = (SP_OP_BLUR, SP_OP_PSF)
 
 _ERRORS = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported"}
 
@@ -91,6 +94,10 @@ SIGNATURES = {
     "sp_rsq_partials": (_I64, [_OPP]),
     "sp_vec_partials": (_I64, [_I64]),
     "sp_dps_residual": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _COP, _P, _P, _P]),
+    "sp_dps_workspace": (_I64, [_OPP, _I64]),
+    "sp_dps_residual_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _COP, _P, _P, _P, _P]),
+    "sp_dps_residual_sched_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P,
+                                                _P]),
     "sp_dps_update": (ctypes.c_int, [_OPP, _P, _P, _P, _P, _P, _P, _P, _U64, _I64, _I64,
                                      _I64, _I64, _COP, _P, _P]),
     "sp_predict_x0": (ctypes.c_int, [_P, _P, _I64, _F, _F, _P, _P]),

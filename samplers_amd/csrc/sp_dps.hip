@@ -413,6 +413,10 @@ bool valid_op(const sp_op* op) {
                    (int64_t)op->channels * op->height * op->width == op->n &&
                    op->height % op->factor == 0 && op->width % op->factor == 0 &&
                    op->m * op->factor * op->factor == op->n;
+        case SP_OP_PSF:
+            return op->taps && op->radius >= 1 && op->radius <= 30 && op->m == op->n &&
+                   op->channels > 0 && (int64_t)op->channels * op->height * op->width == op->n &&
+                   op->height > 2 * op->radius && op->width > 2 * op->radius;
         default: return false;
     }
 }
@@ -435,13 +439,22 @@ int sr_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
 int sr_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
 int sr_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
 
+// point-spread-function blur entry points (sp_psf.hip)
+int64_t psf_partials(const sp_op* op);
+int psf_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
+                     int64_t batch, int64_t y_div, float a, float k, float gs,
+                     const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
+                     float* partial, hipStream_t s);
+int psf_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
+int psf_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
+
 }  // namespace sp
 
 using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 102; }
+int sp_version(void) { return 103; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -508,7 +521,13 @@ int64_t sp_rsq_partials(const sp_op* op) {
     if (!valid_op(op)) return SP_EINVAL;
     if (op->kind == SP_OP_BLUR) return blur_partials(op);
     if (op->kind == SP_OP_SR) return sr_partials(op);
+    if (op->kind == SP_OP_PSF) return psf_partials(op);
     return tiles_elementwise(op->n);
+}
+
+int64_t sp_dps_workspace(const sp_op* op, int64_t batch) {
+    if (!valid_op(op) || batch <= 0) return SP_EINVAL;
+    return op->kind == SP_OP_PSF ? batch * op->m : 0;
 }
 
 int64_t sp_vec_partials(int64_t count) { return count > 0 ? tiles_elementwise(count) : SP_EINVAL; }
@@ -516,11 +535,17 @@ int64_t sp_vec_partials(int64_t count) { return count > 0 ? tiles_elementwise(co
 static int dps_residual_impl(const sp_op* op, const float* x, const float* eps, const float* y,
                              int64_t batch, int64_t y_div, sp_dps_coefs c,
                              const sp_step_rec* sched, const int32_t* cursor, float* v_out,
-                             float* rsq_partial, sp_stream_t stream) {
+                             float* rsq_partial, bool ws, float* work, sp_stream_t stream) {
     if (!valid_op(op) || !x || !eps || !y || !v_out || !rsq_partial || batch <= 0 ||
         y_div <= 0 || batch > 65535)
         return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (op->kind == SP_OP_PSF) {  // two launches through the caller's work buffer (_ws forms)
+        if (!ws) return SP_EUNSUPPORTED;
+        if (!work) return SP_EINVAL;
+        return psf_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
+                                v_out, work, rsq_partial, s);
+    }
     if (op->kind == SP_OP_BLUR)
         return blur_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched,
                                  cursor, v_out, rsq_partial, s);
@@ -549,7 +574,15 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
                     float* rsq_partial, sp_stream_t stream) {
     if (!c) return SP_EINVAL;
     return dps_residual_impl(op, x, eps, y, batch, y_div, *c, nullptr, nullptr, v_out, rsq_partial,
-                             stream);
+                             false, nullptr, stream);
+}
+
+int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                       int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
+                       float* rsq_partial, float* work, sp_stream_t stream) {
+    if (!c) return SP_EINVAL;
+    return dps_residual_impl(op, x, eps, y, batch, y_div, *c, nullptr, nullptr, v_out, rsq_partial,
+                             true, work, stream);
 }
 
 int sp_dps_residual_sched(const sp_op* op, const float* x, const float* eps, const float* y,
@@ -558,7 +591,16 @@ int sp_dps_residual_sched(const sp_op* op, const float* x, const float* eps, con
                           sp_stream_t stream) {
     if (!sched || !cursor) return SP_EINVAL;
     return dps_residual_impl(op, x, eps, y, batch, y_div, sp_dps_coefs{}, sched, cursor, v_out,
-                             rsq_partial, stream);
+                             rsq_partial, false, nullptr, stream);
+}
+
+int sp_dps_residual_sched_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                             int64_t batch, int64_t y_div, const sp_step_rec* sched,
+                             const int32_t* cursor, float* v_out, float* rsq_partial, float* work,
+                             sp_stream_t stream) {
+    if (!sched || !cursor) return SP_EINVAL;
+    return dps_residual_impl(op, x, eps, y, batch, y_div, sp_dps_coefs{}, sched, cursor, v_out,
+                             rsq_partial, true, work, stream);
 }
 
 static int dps_update_impl(const sp_op* op, const float* x, const float* eps, const float* y,
@@ -570,14 +612,15 @@ static int dps_update_impl(const sp_op* op, const float* x, const float* eps, co
     if (!valid_op(op) || !x || !eps || !w || !x_out || batch <= 0 || y_div <= 0 ||
         batch > 65535)
         return SP_EINVAL;
-    if (!v && (op->kind == SP_OP_BLUR || op->kind == SP_OP_SR || !y)) return SP_EINVAL;
+    const bool reads_v = op->kind == SP_OP_BLUR || op->kind == SP_OP_SR || op->kind == SP_OP_PSF;
+    if (!v && (reads_v || !y)) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = static_cast<int>(sp_rsq_partials(op));
     const int Pw = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(Pw, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
-    // BLUR and SR read v: the identity-kind kernel over it (flat Philox element index)
-    const int opk = (op->kind == SP_OP_BLUR || op->kind == SP_OP_SR) ? SP_OP_IDENTITY : op->kind;
+    // BLUR, SR and PSF read v: the identity-kind kernel over it (flat Philox element index)
+    const int opk = reads_v ? SP_OP_IDENTITY : op->kind;
 #define SP_K2(OPK, V, VIN, XIN)                                                            \
     launch_w(TK_DPS_UPDATE, (double)batch, k_dps_update<OPK, V, VIN, XIN>, grid, dim3(kBlock), s, *op, x, eps, y, \
            v, w, rsq_partial, P, xi, seed, step, sample_offset, y_div, c, x_out, sched, cursor)
@@ -709,6 +752,7 @@ int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_str
         }
         case SP_OP_BLUR: return blur_apply(op, x, y, batch, s);
         case SP_OP_SR: return sr_apply(op, x, y, batch, s);
+        case SP_OP_PSF: return psf_apply(op, x, y, batch, s);
     }
     return SP_EINVAL;
 }
@@ -741,6 +785,7 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
         }
         case SP_OP_BLUR: return blur_adjoint(op, y, x, batch, s);
         case SP_OP_SR: return sr_adjoint(op, y, x, batch, s);
+        case SP_OP_PSF: return psf_adjoint(op, y, x, batch, s);
     }
     return SP_EINVAL;
 }

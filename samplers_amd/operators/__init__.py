@@ -12,6 +12,7 @@ from .inpainting import (
     get_mask_side_painting,
 )
 from .linear import GeneralSVDOperator, LinearOperator, SVDOperator
+from .psf import MotionBlurOperator, PSFBlurOperator, motion_blur_kernel
 from .superres import SuperResolutionOperator
 
 __all__ = [
@@ -28,6 +29,9 @@ __all__ = [
     "RandomInpaintingOperator",
     "GaussianBlurOperator",
     "SuperResolutionOperator",
+    "PSFBlurOperator",
+    "MotionBlurOperator",
+    "motion_blur_kernel",
     "get_mask_inpaint_center",
     "get_mask_side_painting",
     "get_mask_random",

@@ -130,7 +130,7 @@ class FusedDPSStep:
             raise NotImplementedError(
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
-                "GaussianBlurOperator and SuperResolutionOperator"
+                "GaussianBlurOperator, SuperResolutionOperator and PSFBlurOperator (and subclasses)"
             )
         _hip.require_cuda(observation_rows, "DPSSampler")
         if observation_rows.dtype != torch.float32:
@@ -170,8 +170,8 @@ class FusedDPSStep:
         # sample; with non-temporal loads and 2 float4 groups per thread it is 7 % faster than
         # re-reading pass 1's v, 42.3 vs 45.2 us at B = 64, 256^2) or re-reads v (reuse_v).
         # Blur always re-reads it (its adjoint needs a halo), and so does super-resolution (v is
-        # constant over a block; pass 2 stays the flat identity-kind kernel).
-        self.needs_v = desc.kind in (_hip.SP_OP_BLUR, _hip.SP_OP_SR) or bool(reuse_v)
+        # constant over a block; pass 2 stays the flat identity-kind kernel) and the PSF blur.
+        self.needs_v = desc.kind in (_hip.SP_OP_BLUR, _hip.SP_OP_SR, _hip.SP_OP_PSF) or bool(reuse_v)
         self.micro_batch = micro_batch
         self.timer = timer
 
@@ -183,6 +183,17 @@ class FusedDPSStep:
         gamma = self.gamma if self.mode == "dps" else float(np.float32(-self.guidance_weight) *
                                                                   np.float32(k))
         return _hip.SpDpsCoefs(a, k, self.grad_scale, br.c_ell, br.c_s, br.std, gamma, 1e-9)
+
+    def workspace(self, batch: int, like: Tensor) -> Tensor | None:
+        """Pass 1's work buffer for ``batch`` samples (``sp_dps_workspace`` floats; None where
+        the operator's pass needs none).  Allocated by torch on the launch stream, so a graph
+        capture records it like every other buffer of the step."""
+        if self.desc.kind != _hip.SP_OP_PSF:  # one-pass kinds: no host call in the step loop
+            return None
+        floats = int(self.lib.sp_dps_workspace(self.desc, batch))
+        if floats < 0:
+            raise _hip.HipLibraryError(f"sp_dps_workspace rejected the descriptor ({floats})")
+        return torch.empty(floats, device=like.device, dtype=torch.float32) if floats else None
 
     def _chunks(self, batch: int):
         mb = self.micro_batch or batch
@@ -212,9 +223,11 @@ class FusedDPSStep:
             span = self.timer.span("dps_residual", bc) if self.timer else None
             if span:
                 span.__enter__()
-            _hip.check(lib.sp_dps_residual(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc), bc,
-                                           self.y_div, coefs, _hip.ptr(v), _hip.ptr(part), stream),
-                       "sp_dps_residual")
+            work = self.workspace(bc, xc)
+            _hip.check(lib.sp_dps_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc), bc,
+                                              self.y_div, coefs, _hip.ptr(v), _hip.ptr(part),
+                                              _hip.ptr(work), stream),
+                       "sp_dps_residual_ws")
             if span:
                 span.__exit__(None, None, None)
             (w,) = torch.autograd.grad(eps, xr, grad_outputs=v.view_as(eps))

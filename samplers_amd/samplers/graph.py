@@ -62,9 +62,11 @@ class GraphedStepLoop:
         b = x.shape[0]
         v = torch.empty_like(x)
         part = torch.empty((b, st.partials), device=x.device, dtype=torch.float32)
-        _hip.check(lib.sp_dps_residual_sched(st.desc, _hip.ptr(x), _hip.ptr(eps_c), _hip.ptr(st.y),
-                                             b, st.y_div, sched, cur, _hip.ptr(v), _hip.ptr(part),
-                                             stream), "sp_dps_residual_sched")
+        work = st.workspace(b, x)  # torch's allocation on the capturing stream: part of the graph
+        _hip.check(lib.sp_dps_residual_sched_ws(st.desc, _hip.ptr(x), _hip.ptr(eps_c),
+                                                _hip.ptr(st.y), b, st.y_div, sched, cur,
+                                                _hip.ptr(v), _hip.ptr(part), _hip.ptr(work),
+                                                stream), "sp_dps_residual_sched_ws")
         (w,) = torch.autograd.grad(eps, xr, grad_outputs=v.view_as(eps))
         w = w.contiguous()
         _hip.check(lib.sp_dps_update_sched(st.desc, _hip.ptr(x), _hip.ptr(eps_c), _hip.ptr(st.y),

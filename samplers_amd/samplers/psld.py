@@ -78,7 +78,8 @@ class FusedPSLDStep:
         self.y_div = int(y_div)
         # operators without a HIP descriptor: A, A^T and their VJPs by torch autograd
         self.generic = desc is None
-        self.blur = not self.generic and desc.kind == _hip.SP_OP_BLUR
+        # kinds with a halo (Gaussian and PSF blur): the pixel pass composed from A and A^T
+        self.blur = not self.generic and desc.kind in _hip.HALO_KINDS
         if self.generic:
             self.n, self.m = int(math.prod(op.x_shape)), int(math.prod(op.y_shape))
         else:
