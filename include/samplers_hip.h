@@ -479,7 +479,12 @@ int sp_wino3x3_bwd_input_ws(const float* dy, const float* up_vjp, int64_t n, int
  * conv output (+ bias).  sp_wino3x3_bwd_input_pool: the input VJP of conv(upsample(x)), dy
  * [n][cout][height][width] -> dx [n][cin][height/2][width/2] (each 2x2 block's sum in
  * sp_upsample2x_vjp's order: bitwise the unfused pair's result when that runs unsplit).
- * Unsplit (no workspace); sp_wino3x3_up_supported says where both directions run. */
+ * Unsplit (no workspace); sp_wino3x3_up_supported says where both directions run.
+ * sp_wino3x3_fwd_up runs 9 of the 16 transformed GEMMs: on a nearest-upsampled image the other
+ * 7 are products with exact zeros (sp_wino.hip, "Live-ξ forms").  For finite x and weights its
+ * output equals sp_wino3x3_fwd on the materialised upsample, the sign of a zero excepted; with
+ * inf or NaN in x or the weights the two can differ (the skipped GEMMs held inf - inf or inf * 0
+ * = NaN, which no longer reaches the output). */
 int sp_wino3x3_up_supported(int32_t cin, int32_t cout, int32_t height, int32_t width);
 int sp_wino3x3_fwd_up(const float* x, const float* up, const float* bias, int64_t n, int32_t cin,
                       int32_t cout, int32_t height, int32_t width, float* y, sp_stream_t stream);

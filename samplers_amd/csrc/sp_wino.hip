@@ -14,7 +14,8 @@
 // barrier per 4 input channels, 4 waves splitting the 16 GEMMs by rows of M and reducing the
 // output transform through LDS): 167-203 effective TFLOP/s, barrier- and wait-bound (42 % of
 // wave time parked); round 3: V shared between the co-half waves through LDS (-0.6 %), a
-// four-way ξ-row split (-1.7 % against the two-way one).
+// four-way ξ-row split (-1.7 % against the two-way one).  The forward fused with a nearest 2x
+// upsample runs only the 9 of the 16 GEMMs whose V is not identically zero ("Live-ξ forms").
 //
 // Numerics: exact fp32 MFMA accumulation of fp32 transforms; the transforms add the
 // usual F(2,3) rounding (|coefficients| <= 1, one 0.5 factor), comparable to MIOpen's
@@ -717,6 +718,68 @@ struct XiRing {
 
 constexpr int XI_EX = 16 * 64 * 4;  // floats per wave of the epilogue exchange
 
+// Live-ξ forms of the fused-upsample forward (UP == 1).  Its LDS image is the nearest-upsampled
+// image and tiles start at even rows and columns, so a lane's window rows 1 and 2 are the same
+// source row and columns 1 and 2 the same source column — at the borders too: the padding is
+// row -1 or row H, never one row of a duplicated pair.  Row 2 of B^T d is then d2 - d1 = +0 and
+// column 2 of V likewise: V_ξ is exactly zero for the 7 ξ with r = 2 or c = 2, for every finite
+// input, and their GEMMs only ever add U * 0.  The 9 live ξ (r, c in {0, 1, 3}) are computed:
+//   1 (form A): the 16-GEMM tile's split (wave H: ξ rows 2H, 2H + 1), the dead MFMAs not issued and
+//     their accumulators a constant zero: 12 MFMAs per k-step in wave 0, 6 in wave 1; what only
+//     the dead ξ consume (U row 2, V row 2) is no longer loaded or computed;
+//   2 (form B, the default): the 9 split 9 / 9.  Group 0 and 1 of wave H are ξ row 3H of channel
+//     block 0 and 1, group 2 is ξ row 1 of channel block H (t1 = d1 + d2 from window rows both
+//     waves hold): 144 accumulator registers per wave, three U pieces per k-step, and an
+//     epilogue exchange of one ξ row (8 KB per wave).
+// Either way every output is the same IEEE sum as the 16-GEMM tile's with its zero terms
+// dropped: equal values, the sign of a zero output excepted.  Inputs or weights that are not
+// finite differ: the dead ξ held inf - inf or inf * 0 = NaN, which no longer reaches the output.
+// (The pooled input VJP, UP == 2, keeps all 16: its pooled output needs only 9 ξ too, but the
+// other 7 cancel only approximately in floating point, and it is pinned bitwise to the unfused
+// pair.)
+#ifndef SP_WINO_UPXI
+#define SP_WINO_UPXI 2
+#endif
+static_assert(SP_WINO_UPXI == 1 || SP_WINO_UPXI == 2, "SP_WINO_UPXI: form A or B");
+template <class GE>
+constexpr int XI_LIVE = GE::UP == 1 ? SP_WINO_UPXI : 0;
+// form A: slot sl of wave H (ξ row 2H + ((sl & 7) >> 2), column sl & 3) is live
+template <class GE, int H>
+constexpr bool xi_live(int sl) {
+    return XI_LIVE<GE> != 1 || ((sl & 3) != 2 && 2 * H + ((sl & 7) >> 2) != 2);
+}
+// form B: ξ row and channel block of wave H's group g, ξ column of a group's i-th accumulator
+constexpr int xil_row(int H, int g) { return g == 2 ? 1 : 3 * H; }
+constexpr int xil_cb(int H, int g) { return g == 2 ? H : g; }
+constexpr int xil_col(int i) { return i == 2 ? 3 : i; }
+
+template <int H>
+__device__ __forceinline__ f32x4 xil_u4(__amdgpu_buffer_rsrc_t urs, int lane, int soff, int g) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                         urs, lane * 64 + 16 * xil_row(H, g), soff + xil_cb(H, g) * 64 * 64, 0));
+}
+
+// form B's V: vn[0..3] = ξ row 3H (t0 = d0 - d2 or t3 = d1 - d3), vn[4..7] = ξ row 1, from
+// window rows e0, e1, e2 (= rows H .. H + 2); column 2 of either is zero and unused
+template <int H>
+__device__ __forceinline__ void xil_half(const WinRow& e0, const WinRow& e1, const WinRow& e2, float* vn) {
+    wpk_v(WinRow{pk_sub(e0.p, e2.p), pk_sub(e0.q, e2.q)}, vn);
+    const WinRow &d1 = H ? e0 : e1, &d2 = H ? e1 : e2;
+    wpk_v(WinRow{pk_add(d1.p, d2.p), pk_add(d1.q, d2.q)}, vn + 4);
+}
+
+#if SP_DEBUG
+// the invariant the live-ξ forms rest on: window rows 1 and 2 bit-equal, columns 1 and 2 too
+template <int H>
+__device__ __forceinline__ void xi_dcheck_dup(const WinRow (&e)[3]) {
+    const WinRow &d1 = e[1 - H], &d2 = e[2 - H];
+    SP_DCHECK(__float_as_uint(d1.p.x) == __float_as_uint(d2.p.x) && __float_as_uint(d1.p.y) == __float_as_uint(d2.p.y) &&
+              __float_as_uint(d1.q.x) == __float_as_uint(d2.q.x) && __float_as_uint(d1.q.y) == __float_as_uint(d2.q.y));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) SP_DCHECK(__float_as_uint(e[i].p.y) == __float_as_uint(e[i].q.x));
+}
+#endif
+
 template <int H>
 __device__ __forceinline__ void xi_load_u(__amdgpu_buffer_rsrc_t urs, int lane, int soff, WrU& u) {
 #pragma unroll
@@ -729,14 +792,15 @@ __device__ __forceinline__ void xi_load_u(__amdgpu_buffer_rsrc_t urs, int lane, 
 }
 
 // this wave's half of V from window rows e0, e1, e2 (= rows H .. H + 2 of the window)
-template <int H>
+// (ROW2 false, form A of the fused upsample: ξ row 2 is zero and not computed)
+template <int H, bool ROW2 = true>
 __device__ __forceinline__ void xi_half(const WinRow& e0, const WinRow& e1, const WinRow& e2, float* vn) {
     const WinRow f{pk_sub(e0.p, e2.p), pk_sub(e0.q, e2.q)};
     if constexpr (H == 0) {  // ξ row 0 = t0 = d0 - d2, row 1 = t1 = d1 + d2
         wpk_v(f, vn);
         wpk_v(WinRow{pk_add(e1.p, e2.p), pk_add(e1.q, e2.q)}, vn + 4);
     } else {                 // ξ row 2 = t2 = d2 - d1, row 3 = t3 = d1 - d3
-        wpk_v(WinRow{pk_sub(e1.p, e0.p), pk_sub(e1.q, e0.q)}, vn);
+        if constexpr (ROW2) wpk_v(WinRow{pk_sub(e1.p, e0.p), pk_sub(e1.q, e0.q)}, vn);
         wpk_v(f, vn + 4);
     }
 }
@@ -757,10 +821,13 @@ __device__ __forceinline__ void xi_step(const WrGeom& g, const WrSrc& cur, const
     float(&vn)[8] = r.v[(K + 1) & 1];
     WinRow e[3];
     const WrX& xb = r.xs[(K + 1) % XI_NR];  // block of step q + 1
-#define XI_MFMA(sl)                                                                               \
-    acc[sl] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.u[2 * ((sl) >> 3) + (((sl) & 7) >> 2)][(sl) & 3], \
-                                                   vc[(sl) & 7], FIRST ? f32x16{} : acc[sl], 0, 0, 0); \
-    __builtin_amdgcn_sched_barrier(0)
+#define XI_MFMA(sl)                                                                                    \
+    if constexpr (xi_live<GE, H>(sl)) {  /* form A of the fused upsample: the dead ξ are not issued */ \
+        acc[sl] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.u[2 * ((sl) >> 3) + (((sl) & 7) >> 2)][(sl) & 3], \
+                                                       vc[(sl) & 7], FIRST ? f32x16{} : acc[sl], 0, 0, 0); \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+    }                                                                                                  \
+    static_assert(true, "")
 #define XI_WALL                                \
     asm volatile("" ::: "memory");             \
     __builtin_amdgcn_sched_barrier(0)
@@ -772,14 +839,17 @@ __device__ __forceinline__ void xi_step(const WrGeom& g, const WrSrc& cur, const
     XI_MFMA(1);
     const int uso = (UN ? nxt.uso : cur.uso) + (UN ? q + XI_DU - g.nsteps : q + XI_DU) * g.u_step * 4;
     WrU& un = r.us[(K + XI_DU) % XI_NR];
+    constexpr bool ROW2 = XI_LIVE<GE> == 1 && H == 1;  // form A: the piece of ξ row 2 is dead
 #if SP_WINO_EXP != 1
-    un.u[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, lane * 64 + 32 * H, uso, 0));
+    if constexpr (!ROW2)
+        un.u[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, lane * 64 + 32 * H, uso, 0));
     un.u[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, lane * 64 + 32 * H + 16, uso, 0));
 #endif
     XI_WALL;
     XI_MFMA(2);
 #if SP_WINO_EXP != 1
-    un.u[2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, lane * 64 + 32 * H, uso + 64 * 64, 0));
+    if constexpr (!ROW2)
+        un.u[2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, lane * 64 + 32 * H, uso + 64 * 64, 0));
     un.u[3] = __builtin_bit_cast(f32x4,
                                  __builtin_amdgcn_raw_buffer_load_b128(urs, lane * 64 + 32 * H + 16, uso + 64 * 64, 0));
 #endif
@@ -799,13 +869,16 @@ __device__ __forceinline__ void xi_step(const WrGeom& g, const WrSrc& cur, const
     XI_WALL;
     XI_MFMA(6);
     e[2] = wr_window_row<GE>(xw, xl, H + 2);
+#if SP_DEBUG
+    if constexpr (GE::UP == 1) xi_dcheck_dup<H>(e);
+#endif
     XI_WALL;
     XI_MFMA(7);
     XI_MFMA(8);
     XI_MFMA(9);
     XI_MFMA(10);
     XI_MFMA(11);
-    xi_half<H>(e[0], e[1], e[2], vn);
+    xi_half<H, XI_LIVE<GE> != 1>(e[0], e[1], e[2], vn);
     XI_WALL;
     XI_MFMA(12);
     XI_MFMA(13);
@@ -813,39 +886,118 @@ __device__ __forceinline__ void xi_step(const WrGeom& g, const WrSrc& cur, const
     XI_MFMA(15);
     XI_WALL;
 #undef XI_MFMA
+}
+
+// The k-step of form B of the fused upsample (SP_WINO_UPXI): 9 MFMAs, accumulator 3 g + i is
+// group g's ξ column xil_col(i); the same side work in the same order beside them, with three U
+// pieces and the window read three MFMAs ahead of the transform.
+template <class GE, int H, int K, bool FIRST, bool XN, bool UN>
+__device__ __forceinline__ void xil_step(const WrGeom& g, const WrSrc& cur, const WrSrc& nxt,
+                                         __amdgpu_buffer_rsrc_t urs, int lane, float* xw,
+                                         const WxLane& xl, int q, XiRing& r, f32x16 (&acc)[9]) {
+    asm volatile("" : "+s"(q));  // as xi_step
+    const WrU& u = r.us[K];
+    const float(&vc)[8] = r.v[K & 1];
+    float(&vn)[8] = r.v[(K + 1) & 1];
+    WinRow e[3];
+    const WrX& xb = r.xs[(K + 1) % XI_NR];  // block of step q + 1
+#define XIL_MFMA(s)                                                                                  \
+    acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(u.u[(s) / 3][xil_col((s) % 3)],                     \
+                                                  vc[((s) / 3 == 2 ? 4 : 0) + xil_col((s) % 3)],      \
+                                                  FIRST ? f32x16{} : acc[s], 0, 0, 0);                \
+    __builtin_amdgcn_sched_barrier(0)
+    XIL_MFMA(0);
+#if SP_WINO_EXP != 1
+    wr_load_x<GE>(XN ? nxt : cur, (XN ? q + XI_DX - g.nsteps : q + XI_DX) * g.so_step, r.xs[(K + XI_DX) % XI_NR]);
+#endif
+    XI_WALL;
+    XIL_MFMA(1);
+    const int uso = (UN ? nxt.uso : cur.uso) + (UN ? q + XI_DU - g.nsteps : q + XI_DU) * g.u_step * 4;
+    WrU& un = r.us[(K + XI_DU) % XI_NR];
+#if SP_WINO_EXP != 1
+    un.u[0] = xil_u4<H>(urs, lane, uso, 0);
+    un.u[1] = xil_u4<H>(urs, lane, uso, 1);
+#endif
+    XI_WALL;
+    XIL_MFMA(2);
+#if SP_WINO_EXP != 1
+    un.u[2] = xil_u4<H>(urs, lane, uso, 2);
+#endif
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xw[xl.wa + i] = xb.a[i];
+    XI_WALL;
+    XIL_MFMA(3);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xw[xl.wb + i] = xb.b[i];
+    xw[xl.wh] = xb.h;
+    XI_WALL;
+    XIL_MFMA(4);
+    e[0] = wr_window_row<GE>(xw, xl, H + 0);
+    e[1] = wr_window_row<GE>(xw, xl, H + 1);
+    e[2] = wr_window_row<GE>(xw, xl, H + 2);
+#if SP_DEBUG
+    xi_dcheck_dup<H>(e);
+#endif
+    XI_WALL;
+    XIL_MFMA(5);
+    XIL_MFMA(6);
+    XIL_MFMA(7);
+    xil_half<H>(e[0], e[1], e[2], vn);
+    XI_WALL;
+    XIL_MFMA(8);
+    XI_WALL;
+#undef XIL_MFMA
 #undef XI_WALL
+}
+
+template <class GE, int H, int K, bool FIRST, bool XN, bool UN, int NA>
+__device__ __forceinline__ void xi_step_any(const WrGeom& g, const WrSrc& cur, const WrSrc& nxt,
+                                            __amdgpu_buffer_rsrc_t urs, int lane, float* xw,
+                                            const WxLane& xl, int q, XiRing& r, f32x16 (&acc)[NA]) {
+    if constexpr (XI_LIVE<GE> == 2) xil_step<GE, H, K, FIRST, XN, UN>(g, cur, nxt, urs, lane, xw, xl, q, r, acc);
+    else xi_step<GE, H, K, FIRST, XN, UN>(g, cur, nxt, urs, lane, xw, xl, q, r, acc);
 }
 
 // k-steps p + K0 + K for K in the sequence (p % XI_NR == 0).  LAST: the tile's final XI_NR
 // steps, whose loads beyond the tile's last step fetch the next tile's first steps.
-template <class GE, int H, bool FIRST, bool LAST, int K0, int... K>
+template <class GE, int H, bool FIRST, bool LAST, int K0, int NA, int... K>
 __device__ __forceinline__ void xi_steps(std::integer_sequence<int, K...>, const WrGeom& g, const WrSrc& cur,
                                          const WrSrc& nxt, __amdgpu_buffer_rsrc_t urs, int lane, float* xw,
-                                         const WxLane& xl, int p, XiRing& r, f32x16 (&acc)[16]) {
-    (xi_step<GE, H, K0 + K, FIRST && K0 + K == 0, LAST && (K0 + K + XI_DX >= XI_NR),
-             LAST && (K0 + K + XI_DU >= XI_NR)>(g, cur, nxt, urs, lane, xw, xl, p + K0 + K, r, acc),
+                                         const WxLane& xl, int p, XiRing& r, f32x16 (&acc)[NA]) {
+    (xi_step_any<GE, H, K0 + K, FIRST && K0 + K == 0, LAST && (K0 + K + XI_DX >= XI_NR),
+                 LAST && (K0 + K + XI_DU >= XI_NR)>(g, cur, nxt, urs, lane, xw, xl, p + K0 + K, r, acc),
      ...);
 }
 
 // Epilogue: row sums of this wave's ξ rows for both channel blocks; the block the partner
 // completes goes through LDS, the partner's rows of this wave's block come back; then the
 // output transform, bias, residual and stores as wr_epilogue (same order of operations).
-template <class GE, int H, bool RES>
+// (Form B of the fused upsample, 9 accumulators: the partner's block needs this wave's ξ row 3H
+// alone, two sums per accumulator register; the zero terms of ξ row 2 and ξ column 2 are dropped
+// from every sum and the order of the remaining additions is kept.)
+template <class GE, int H, bool RES, int NA>
 __device__ __forceinline__ void xi_epilogue(const WrGeom& g, const WrTile& ti, int wv, int lane,
-                                            const f32x16 (&acc)[16], const WrRes& rv, float* ex) {
-
-    float* mine = ex + H * XI_EX;          // written by this wave (the partner's block)
-    const float* theirs = ex + (1 - H) * XI_EX;
+                                            const f32x16 (&acc)[NA], const WrRes& rv, float* ex) {
+    constexpr bool LB = XI_LIVE<GE> == 2;
+    constexpr int EX = LB ? XI_EX / 2 : XI_EX;
+    float* mine = ex + H * EX;             // written by this wave (the partner's block)
+    const float* theirs = ex + (1 - H) * EX;
 #pragma unroll
     for (int rr = 0; rr < 16; ++rr) {
-        float o[4];
+        if constexpr (LB) {
+            constexpr int b = 3 * (1 - H);  // group 1 - H: the partner's channel block, ξ row 3H
+            *reinterpret_cast<f32x2*>(mine + (rr * 64 + lane) * 2) =
+                f32x2{acc[b + 0][rr] + acc[b + 1][rr], acc[b + 1][rr] - acc[b + 2][rr]};
+        } else {
+            float o[4];
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int b = (1 - H) * 8 + a * 4;  // the partner's channel block, ξ row 2H + a
-            o[a] = acc[b + 0][rr] + acc[b + 1][rr] + acc[b + 2][rr];
-            o[2 + a] = acc[b + 1][rr] - acc[b + 2][rr] - acc[b + 3][rr];
+            for (int a = 0; a < 2; ++a) {
+                const int b = (1 - H) * 8 + a * 4;  // the partner's channel block, ξ row 2H + a
+                o[a] = acc[b + 0][rr] + acc[b + 1][rr] + acc[b + 2][rr];
+                o[2 + a] = acc[b + 1][rr] - acc[b + 2][rr] - acc[b + 3][rr];
+            }
+            *reinterpret_cast<f32x4*>(mine + (rr * 64 + lane) * 4) = f32x4{o[0], o[1], o[2], o[3]};
         }
-        *reinterpret_cast<f32x4*>(mine + (rr * 64 + lane) * 4) = f32x4{o[0], o[1], o[2], o[3]};
         __builtin_amdgcn_sched_barrier(0);
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -870,23 +1022,39 @@ __device__ __forceinline__ void xi_epilogue(const WrGeom& g, const WrTile& ti, i
     const float bl = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(brs, (tf.co0 + l) * 4, 0, 0));
 #pragma unroll
     for (int rr = 0; rr < 16; ++rr) {
-        const f32x4 p = *reinterpret_cast<const f32x4*>(theirs + (rr * 64 + lane) * 4);
         float s0[4], s1[4];
+        if constexpr (LB) {  // own ξ row 3H (group H) and row 1 (group 2); the partner's row 3 (1 - H)
+            const f32x2 p = *reinterpret_cast<const f32x2*>(theirs + (rr * 64 + lane) * 2);
+            s0[3 * H] = acc[3 * H + 0][rr] + acc[3 * H + 1][rr];
+            s1[3 * H] = acc[3 * H + 1][rr] - acc[3 * H + 2][rr];
+            s0[1] = acc[6][rr] + acc[7][rr];
+            s1[1] = acc[7][rr] - acc[8][rr];
+            s0[3 * (1 - H)] = p.x;
+            s1[3 * (1 - H)] = p.y;
+        } else {
+            const f32x4 p = *reinterpret_cast<const f32x4*>(theirs + (rr * 64 + lane) * 4);
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int b = H * 8 + a * 4;  // this wave's rows of its own block: ξ row 2H + a
-            s0[2 * H + a] = acc[b + 0][rr] + acc[b + 1][rr] + acc[b + 2][rr];
-            s1[2 * H + a] = acc[b + 1][rr] - acc[b + 2][rr] - acc[b + 3][rr];
-            s0[2 * (1 - H) + a] = p[a];
-            s1[2 * (1 - H) + a] = p[2 + a];
+            for (int a = 0; a < 2; ++a) {
+                const int b = H * 8 + a * 4;  // this wave's rows of its own block: ξ row 2H + a
+                s0[2 * H + a] = acc[b + 0][rr] + acc[b + 1][rr] + acc[b + 2][rr];
+                s1[2 * H + a] = acc[b + 1][rr] - acc[b + 2][rr] - acc[b + 3][rr];
+                s0[2 * (1 - H) + a] = p[a];
+                s1[2 * (1 - H) + a] = p[2 + a];
+            }
         }
         const int c = (rr & 3) + 8 * (rr >> 2);
         const float b0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bl), c));
         const float b1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bl), c + 4));
         const float bv = hh ? b1 : b0;
         const int so = c * pout * 4;
-        f32x2 y0 = {s0[0] + s0[1] + s0[2] + bv, s1[0] + s1[1] + s1[2] + bv};
-        f32x2 y1 = {s0[1] - s0[2] - s0[3] + bv, s1[1] - s1[2] - s1[3] + bv};
+        f32x2 y0, y1;
+        if constexpr (LB) {
+            y0 = f32x2{s0[0] + s0[1] + bv, s1[0] + s1[1] + bv};
+            y1 = f32x2{s0[1] - s0[3] + bv, s1[1] - s1[3] + bv};
+        } else {
+            y0 = f32x2{s0[0] + s0[1] + s0[2] + bv, s1[0] + s1[1] + s1[2] + bv};
+            y1 = f32x2{s0[1] - s0[2] - s0[3] + bv, s1[1] - s1[2] - s1[3] + bv};
+        }
         if constexpr (RES) y0 += rv.v[rr][0], y1 += rv.v[rr][1];
         if constexpr (GE::UP == 2) {  // k_upsample2x_vjp's order: ((row 0) + row 1, left first)
             const float p = ((y0.x + y0.y) + y1.x) + y1.y;
@@ -903,7 +1071,7 @@ __device__ __forceinline__ void xi_epilogue(const WrGeom& g, const WrTile& ti, i
 
 template <class GE, bool RES, int H>
 __device__ __forceinline__ void xi_body(const WrGeom& g, int wv, int lane, float* xw, float* ex) {
-
+    constexpr int LV = XI_LIVE<GE>;  // the fused upsample's live-ξ form, else 0
     const int wq = wv & ~1;  // tile geometry of channel half 0 (the pair covers all 64 channels)
     WxLane xl;
     {
@@ -933,16 +1101,30 @@ __device__ __forceinline__ void xi_body(const WrGeom& g, int wv, int lane, float
         constexpr int s = decltype(S)::value;
         if constexpr (s < XI_DX) wr_load_x<GE>(cur, s * g.so_step, r.xs[s]);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (s < XI_DU) xi_load_u<H>(urs, lane, cur.uso + s * static_cast<int>(g.u_step) * 4, r.us[s]);
+        if constexpr (s < XI_DU) {
+            const int uso = cur.uso + s * static_cast<int>(g.u_step) * 4;
+            if constexpr (LV == 2) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) r.us[s].u[i] = xil_u4<H>(urs, lane, uso, i);
+            } else {
+                xi_load_u<H>(urs, lane, uso, r.us[s]);
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
     });
     {
         wr_stage_x(xw, xl, r.xs[0]);
         const WinRow e0 = wr_window_row<GE>(xw, xl, H + 0), e1 = wr_window_row<GE>(xw, xl, H + 1),
                      e2 = wr_window_row<GE>(xw, xl, H + 2);
-        xi_half<H>(e0, e1, e2, r.v[0]);
+        if constexpr (LV == 2) xil_half<H>(e0, e1, e2, r.v[0]);
+        else xi_half<H, LV != 1>(e0, e1, e2, r.v[0]);
     }
-    f32x16 acc[16];
+    f32x16 acc[LV == 2 ? 9 : 16];
+    if constexpr (LV == 1) {  // the dead ξ: zero once, never written again
+#pragma unroll
+        for (int sl = 0; sl < 16; ++sl)
+            if (!xi_live<GE, H>(sl)) acc[sl] = f32x16{};
+    }
     const int last = g.nsteps - XI_NR;  // >= XI_NR, a multiple of XI_NR (wino3x3's dispatch rule)
     constexpr auto ring = std::make_integer_sequence<int, XI_NR>{};
     // the residual (RES: 64 registers per lane) is loaded two steps before the tile's end, so it
@@ -981,11 +1163,12 @@ template <bool RES, int TCW, int UP = 0>
 __global__ __launch_bounds__(kBlock, 1) void k_wino3x3_xi(WrGeom g) {
     using GE = WGeo<TCW, false, false, UP>;
     __shared__ __attribute__((aligned(16))) float xlds[4 * GE::WAVE];
-    __shared__ __attribute__((aligned(16))) float exlds[2 * 2 * XI_EX];  // [pair][writer][...]
+    constexpr int EX = XI_LIVE<GE> == 2 ? XI_EX / 2 : XI_EX;  // form B exchanges one ξ row
+    __shared__ __attribute__((aligned(16))) float exlds[2 * 2 * EX];  // [pair][writer][...]
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float* const xw = xlds + wv * GE::WAVE;
-    float* const ex = exlds + (wv >> 1) * 2 * XI_EX;
+    float* const ex = exlds + (wv >> 1) * 2 * EX;
     if (wv & 1) xi_body<GE, RES, 1>(g, wv, lane, xw, ex);
     else xi_body<GE, RES, 0>(g, wv, lane, xw, ex);
 }
@@ -1148,7 +1331,8 @@ static int wino3x3(int kind, const float* x, const float* up, const float* bias,
     const int grid = static_cast<int>(std::min<int64_t>(tiles * ksplit, cu_count()));
     // executed MFMA work: 16 GEMMs of 2*cin*cout per 2x2 tile = 8*cin*cout per pixel
     // (the direct-conv equivalent is 18*cin*cout per pixel, 2.25x more)
-    const double flops = 8.0 * n * cin * cout * height * width;
+    // (the fused upsample's forward issues the 9 live ones: 4.5*cin*cout per pixel)
+    const double flops = (up_mode == 1 ? 4.5 : 8.0) * n * cin * cout * height * width;
     const dim3 gd(static_cast<unsigned>(grid)), bd(kBlock);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (up_mode == 1) {
