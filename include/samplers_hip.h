@@ -28,6 +28,9 @@
  *     sp_pixel_opt_step, sp_ddim_eps_step, sp_stochastic_resample.  Packed INPAINT observation
  *     rows (m elements) and partial-sum buffers are read by scalar loads and need only 4-byte
  *     alignment.  With n % 4 != 0 all access is scalar and 4-byte alignment suffices.
+ *     PHASE: the kind's own launches read x, eps, y, g and write y, v, dx by scalar access (any
+ *     width, any pads, 4-byte alignment); its workspace holds (re, im) pairs and must be 8-byte
+ *     aligned.  Pass 2 over its v follows the rule above (n % 4 == 0 -> 16-byte aligned rows).
  */
 #ifndef SAMPLERS_HIP_H
 #define SAMPLERS_HIP_H
@@ -59,10 +62,17 @@ enum {
                            average pooling of every channel plane (factor 2, 4
                            or 8 dividing height and width, m = n / factor^2);
                            adjoint = exact transpose, A^+ = factor^2 A^T       */
-    SP_OP_PSF = 5       /* new: depthwise dense 2-D point-spread function of
+    SP_OP_PSF = 5,      /* new: depthwise dense 2-D point-spread function of
                            (2*radius+1)^2 taps (motion blur, defocus, measured
                            PSFs), correlation with reflect padding; adjoint =
                            exact transpose; no pseudo-inverse; m == n           */
+    SP_OP_PHASE = 6     /* new, NONLINEAR: Fourier phase retrieval,
+                           y = |FFT2(zero-pad(x))| per channel plane, norm "ortho",
+                           unshifted (DC at [0][0]); pad_h = radius rows and
+                           pad_w = factor columns of zeros on each side; the padded
+                           sizes Nh = height + 2*radius, Nw = width + 2*factor are
+                           2^k or 3*2^k in [8, 1024]; m = channels*Nh*Nw.  No
+                           adjoint: sp_op_apply_ws / sp_op_vjp_ws                */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -78,8 +88,12 @@ typedef struct sp_op {
     const float* taps;               /* BLUR: 2*radius+1 normalised taps.  PSF: the
                                         dense row-major (2*radius+1)^2 taps, used
                                         as given (any finite values)            */
-    int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30                */
-    int32_t factor;                  /* SR: 2, 4 or 8 (0 for the other kinds)  */
+    int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
+                                        zero rows added above and below         */
+    int32_t factor;                  /* SR: 2, 4 or 8.  PHASE: pad_w >= 0, zero
+                                        columns added left and right (0 for the
+                                        other kinds).  PHASE: keep_bits, word_rank
+                                        and taps must be NULL                   */
 } sp_op;
 
 /* Scalars of one DPS step (all fp32, computed on the host exactly as the
@@ -155,13 +169,20 @@ int sp_debug_selftest(sp_stream_t stream);
  * channels * height * width != n, a spatial size not divisible by the factor, or
  * m * factor^2 != n).  PSF: the 32 x 64 tiles per sample of its residual launch; rejected
  * unless taps != NULL, 1 <= radius <= 30, m == n == channels * height * width and
- * height, width > 2 * radius. */
+ * height, width > 2 * radius.  PHASE: the column tiles per sample of its column launch
+ * (csrc/sp_phase.hip); rejected unless radius, factor >= 0, both padded sizes are 2^k or 3*2^k in
+ * [8, 1024], n == channels*height*width, m == channels*Nh*Nw and keep_bits, word_rank and taps
+ * are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
 /* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
  * 0 for every kind but PSF (one pass, no workspace), batch * m for PSF (its residual launch
- * leaves grad_scale * r there for the adjoint launch).  SP_EINVAL for a rejected descriptor
+ * leaves grad_scale * r there for the adjoint launch), 2 * batch * channels * Nw * height for
+ * PHASE (the complex row transforms, stored transposed).  SP_EINVAL for a rejected descriptor
  * or batch <= 0.  The library allocates nothing. */
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
+/* Floats of `work` that sp_op_apply_ws / sp_op_vjp_ws need: 0 for the linear kinds, the figure
+ * of sp_dps_workspace for PHASE.  SP_EINVAL for a rejected descriptor or batch <= 0. */
+int64_t sp_op_workspace(const sp_op* op, int64_t batch);
 
 /* DPS pass 1 — replaces dps.py:99-103 up to the prior's VJP and dps.py:117-118:
  *   x0  = (x - k*eps)/a                         (networks/base.py:41-43)
@@ -178,7 +199,11 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  * sp_dps_residual).  PSF runs here only (sp_dps_residual / _sched return SP_EUNSUPPORTED for
  * it), as two launches: `residual` forms x0 while staging its tile, writes
  * work = grad_scale * (y - A x0) and one |r|^2 partial per tile, `adjoint` gathers
- * v = A^T work (csrc/sp_psf.hip).  work must not alias any other argument. */
+ * v = A^T work (csrc/sp_psf.hip).  PHASE runs here only too, as three launches
+ * (csrc/sp_phase.hip): row FFTs of x0 -> work; per column tile the forward column FFT,
+ * r = y - |z|, one r^2 partial, u = grad_scale * r * z/|z| (0 at |z| = 0) and the inverse column
+ * FFT, in LDS, back into work; inverse row FFTs, real part, crop -> v = J(x0)^T(grad_scale * r).
+ * work must not alias any other argument. */
 int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
                        int64_t batch, int64_t y_div, const sp_dps_coefs* c,
                        float* v_out, float* rsq_partial, float* work, sp_stream_t stream);
@@ -188,7 +213,7 @@ int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const 
  *   g   = v/a - (k/a) * w          (w = J_eps^T v from the prior's VJP)
  *   x'  = c_ell*x + c_s*x0 + std*xi + gamma/(sqrt(sum_p rsq_partial[b][p]) + norm_eps) * g
  * v: pass NULL to recompute v from (x, eps, y) (IDENTITY/INPAINT/MASK), else
- *    the buffer written by sp_dps_residual (required for BLUR, SR and PSF, which run the
+ *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF and PHASE, which run the
  *    identity-kind update over it: the Philox element index stays the flat element index).
  * rsq_partial: NULL selects a fixed factor, x' = ... + gamma * g — the PGDM update
  *    (pgdm.py:126-135, gamma = -guidance_weight*sqrt(1-acp_t), v = -2 A^T r) and the
@@ -221,6 +246,16 @@ int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_str
  * each block (exact); the pseudo-inverse is factor^2 times this.  PSF: a gather (no atomics):
  * the zero-extended correlation plus the fold terms of the reflect padding, in a fixed order. */
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream);
+/* y = A(x) with a workspace of sp_op_workspace floats: sp_op_apply for the linear kinds (work
+ * unused, may be NULL); PHASE: y = |FFT2(pad(x))| (sp_op_apply and sp_op_adjoint return
+ * SP_EUNSUPPORTED for PHASE, as do sp_psld_pixel, sp_psld_cotangent and sp_pixel_opt_step). */
+int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                   sp_stream_t stream);
+/* dx = J(x)^T g for the nonlinear kinds (g: batch rows of m, dx: batch rows of n).  PHASE:
+ * crop(Re(IFFT2(g * z/|z|))) with z = FFT2(pad(x)) recomputed, z/|z| = 0 at |z| = 0 (never NaN
+ * or inf).  SP_EUNSUPPORTED for the linear kinds, whose VJP is sp_op_adjoint. */
+int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
+                 float* work, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
  *   r = y[b/y_div] - z[b];  g[b] = grad_scale * r;  rsq_partial[b][p] += r^2 partials.

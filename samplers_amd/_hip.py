@@ -18,6 +18,7 @@ LIB_PATH = Path(__file__).resolve().parent / "lib" / "libsamplers_hip.so"
 DEBUG_LIB_PATH = Path(__file__).resolve().parent / "lib" / "debug" / "libsamplers_hip.so"
 
 SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR, SP_OP_PSF = 0, 1, 2, 3, 4, 5
+SP_OP_PHASE = 6  # nonlinear: sp_op_apply_ws / sp_op_vjp_ws, no adjoint
 # kinds whose adjoint needs a halo: no fused PSLD / pixel-optimisation pass, the samplers compose
 # them from sp_op_apply / sp_op_adjoint
 HALO_KINDS = (SP_OP_BLUR, SP_OP_PSF)
@@ -104,6 +105,9 @@ SIGNATURES = {
     "sp_randn": (ctypes.c_int, [_P, _I64, _I64, _U64, _I64, _I64, _P]),
     "sp_op_apply": (ctypes.c_int, [_OPP, _P, _P, _I64, _P]),
     "sp_op_adjoint": (ctypes.c_int, [_OPP, _P, _P, _I64, _P]),
+    "sp_op_workspace": (_I64, [_OPP, _I64]),
+    "sp_op_apply_ws": (ctypes.c_int, [_OPP, _P, _P, _I64, _P, _P]),
+    "sp_op_vjp_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _P, _P]),
     "sp_residual_grad": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "sp_psld_pixel": (ctypes.c_int, [_OPP, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "sp_sum_partials": (ctypes.c_int, [_P, _I64, _P, _P]),

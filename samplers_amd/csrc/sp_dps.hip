@@ -397,6 +397,8 @@ int64_t tiles_elementwise(int64_t n) {
     return cdiv(n, (int64_t)kIter * kBlock * V);
 }
 
+bool phase_size_ok(int N);  // sp_phase.hip: 2^k or 3 * 2^k in [8, 1024]
+
 bool valid_op(const sp_op* op) {
     if (!op || op->n <= 0 || op->m <= 0) return false;
     switch (op->kind) {
@@ -417,6 +419,15 @@ bool valid_op(const sp_op* op) {
             return op->taps && op->radius >= 1 && op->radius <= 30 && op->m == op->n &&
                    op->channels > 0 && (int64_t)op->channels * op->height * op->width == op->n &&
                    op->height > 2 * op->radius && op->width > 2 * op->radius;
+        case SP_OP_PHASE:  // radius = pad_h, factor = pad_w
+            return !op->taps && !op->keep_bits && !op->word_rank && op->radius >= 0 &&
+                   op->factor >= 0 && op->channels > 0 && op->height > 0 && op->width > 0 &&
+                   op->height <= 1024 && op->width <= 1024 && op->radius <= 512 && op->factor <= 512 &&
+                   phase_size_ok(op->height + 2 * op->radius) &&
+                   phase_size_ok(op->width + 2 * op->factor) &&
+                   (int64_t)op->channels * op->height * op->width == op->n &&
+                   (int64_t)op->channels * (op->height + 2 * op->radius) *
+                           (op->width + 2 * op->factor) == op->m;
         default: return false;
     }
 }
@@ -448,13 +459,24 @@ int psf_dps_residual(const sp_op* op, const float* x, const float* eps, const fl
 int psf_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
 int psf_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
 
+// Fourier phase retrieval entry points (sp_phase.hip)
+int64_t phase_partials(const sp_op* op);
+int64_t phase_workspace(const sp_op* op, int64_t batch);
+int phase_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
+                       int64_t batch, int64_t y_div, float a, float k, float gs,
+                       const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
+                       float* partial, hipStream_t s);
+int phase_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work, hipStream_t s);
+int phase_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
+              float* work, hipStream_t s);
+
 }  // namespace sp
 
 using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 103; }
+int sp_version(void) { return 104; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -522,12 +544,19 @@ int64_t sp_rsq_partials(const sp_op* op) {
     if (op->kind == SP_OP_BLUR) return blur_partials(op);
     if (op->kind == SP_OP_SR) return sr_partials(op);
     if (op->kind == SP_OP_PSF) return psf_partials(op);
+    if (op->kind == SP_OP_PHASE) return phase_partials(op);
     return tiles_elementwise(op->n);
 }
 
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch) {
     if (!valid_op(op) || batch <= 0) return SP_EINVAL;
+    if (op->kind == SP_OP_PHASE) return phase_workspace(op, batch);
     return op->kind == SP_OP_PSF ? batch * op->m : 0;
+}
+
+int64_t sp_op_workspace(const sp_op* op, int64_t batch) {
+    if (!valid_op(op) || batch <= 0) return SP_EINVAL;
+    return op->kind == SP_OP_PHASE ? phase_workspace(op, batch) : 0;
 }
 
 int64_t sp_vec_partials(int64_t count) { return count > 0 ? tiles_elementwise(count) : SP_EINVAL; }
@@ -545,6 +574,12 @@ static int dps_residual_impl(const sp_op* op, const float* x, const float* eps, 
         if (!work) return SP_EINVAL;
         return psf_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
                                 v_out, work, rsq_partial, s);
+    }
+    if (op->kind == SP_OP_PHASE) {  // three launches through the work buffer (_ws forms)
+        if (!ws) return SP_EUNSUPPORTED;
+        if (!work) return SP_EINVAL;
+        return phase_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
+                                  v_out, work, rsq_partial, s);
     }
     if (op->kind == SP_OP_BLUR)
         return blur_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched,
@@ -612,14 +647,15 @@ static int dps_update_impl(const sp_op* op, const float* x, const float* eps, co
     if (!valid_op(op) || !x || !eps || !w || !x_out || batch <= 0 || y_div <= 0 ||
         batch > 65535)
         return SP_EINVAL;
-    const bool reads_v = op->kind == SP_OP_BLUR || op->kind == SP_OP_SR || op->kind == SP_OP_PSF;
+    const bool reads_v = op->kind == SP_OP_BLUR || op->kind == SP_OP_SR || op->kind == SP_OP_PSF ||
+                         op->kind == SP_OP_PHASE;
     if (!v && (reads_v || !y)) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = static_cast<int>(sp_rsq_partials(op));
     const int Pw = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(Pw, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
-    // BLUR, SR and PSF read v: the identity-kind kernel over it (flat Philox element index)
+    // BLUR, SR, PSF and PHASE read v: the identity-kind kernel over it (flat Philox element index)
     const int opk = reads_v ? SP_OP_IDENTITY : op->kind;
 #define SP_K2(OPK, V, VIN, XIN)                                                            \
     launch_w(TK_DPS_UPDATE, (double)batch, k_dps_update<OPK, V, VIN, XIN>, grid, dim3(kBlock), s, *op, x, eps, y, \
@@ -753,8 +789,25 @@ int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_str
         case SP_OP_BLUR: return blur_apply(op, x, y, batch, s);
         case SP_OP_SR: return sr_apply(op, x, y, batch, s);
         case SP_OP_PSF: return psf_apply(op, x, y, batch, s);
+        case SP_OP_PHASE: return SP_EUNSUPPORTED;  // needs a workspace: sp_op_apply_ws
     }
     return SP_EINVAL;
+}
+
+int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                   sp_stream_t stream) {
+    if (!valid_op(op)) return SP_EINVAL;
+    if (op->kind != SP_OP_PHASE) return sp_op_apply(op, x, y, batch, stream);
+    if (!x || !y || !work || batch <= 0 || batch > 65535) return SP_EINVAL;
+    return phase_apply(op, x, y, batch, work, static_cast<hipStream_t>(stream));
+}
+
+int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
+                 float* work, sp_stream_t stream) {
+    if (!valid_op(op)) return SP_EINVAL;
+    if (op->kind != SP_OP_PHASE) return SP_EUNSUPPORTED;  // linear kinds: sp_op_adjoint
+    if (!x || !g || !dx || !work || batch <= 0 || batch > 65535) return SP_EINVAL;
+    return phase_vjp(op, x, g, dx, batch, work, static_cast<hipStream_t>(stream));
 }
 
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream) {
@@ -786,6 +839,7 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
         case SP_OP_BLUR: return blur_adjoint(op, y, x, batch, s);
         case SP_OP_SR: return sr_adjoint(op, y, x, batch, s);
         case SP_OP_PSF: return psf_adjoint(op, y, x, batch, s);
+        case SP_OP_PHASE: return SP_EUNSUPPORTED;  // nonlinear: sp_op_vjp_ws
     }
     return SP_EINVAL;
 }

@@ -339,8 +339,9 @@ int sp_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batc
     if (!valid_op(op) || !x0 || !y || !x_eff || !atr || !rsq_partial || batch <= 0 ||
         batch > 65535 || y_div <= 0)
         return SP_EINVAL;
-    if (op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF)
+    if (op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF || op->kind == SP_OP_PHASE)
         return SP_EUNSUPPORTED;  // kinds with a halo: composed from apply/adjoint by the caller
+                                 // (PHASE is nonlinear: no adjoint, no PSLD)
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (op->kind == SP_OP_SR) return sr_psld_pixel(op, x0, y, batch, y_div, x_eff, atr, rsq_partial, s);
     const int P = static_cast<int>(tiles_elementwise(op->n));
@@ -382,6 +383,7 @@ int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const f
                       sp_stream_t stream) {
     if (!valid_op(op) || !atr || !u || !norm_sq || !out || batch <= 0 || batch > 65535)
         return SP_EINVAL;
+    if (op->kind == SP_OP_PHASE) return SP_EUNSUPPORTED;  // nonlinear: no A^T A
     if ((op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF) && !ata_u) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (op->kind == SP_OP_SR) return sr_psld_cotangent(op, atr, u, norm_sq, omega, batch, out, s);
@@ -460,7 +462,8 @@ int sp_pixel_opt_step(const sp_op* op, float* x, float* exp_avg, float* exp_avg_
     if (!valid_op(op) || !x || !exp_avg || !exp_avg_sq || !y || !c || !rsq_partial ||
         batch <= 0 || batch > 65535 || y_div <= 0)
         return SP_EINVAL;
-    if (op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF) return SP_EUNSUPPORTED;  // composed by the caller
+    if (op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF || op->kind == SP_OP_PHASE)
+        return SP_EUNSUPPORTED;  // composed by the caller (PHASE: nonlinear, no adjoint)
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (op->kind == SP_OP_SR)
         return sr_pixel_opt(op, x, exp_avg, exp_avg_sq, y, batch, y_div, grad_scale, c, stop,

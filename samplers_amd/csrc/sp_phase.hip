@@ -1,0 +1,446 @@
+// Fourier phase retrieval (SP_OP_PHASE): y = |FFT2(zero-pad(x))| per channel plane, norm "ortho",
+// unshifted (DC at [0][0]); the reference has no such operator, semantics in
+// operators/phase.py, pinned in fp64 by tests/phase_ops.py.  x is (C, H, W), padded by
+// pad_h = op.radius rows and pad_w = op.factor columns on each side to Nh x Nw, each 2^k or
+// 3 * 2^k in [8, 1024].  With z = FFT2(pad(x)) the Jacobian-transpose product of a y-space
+// cotangent g is  J^T g = crop(Re(IFFT2(g * z / |z|)))  with z / |z| := 0 at |z| = 0.
+//
+// Three launches through the caller's workspace, shared by apply (1, 2), the VJP (1, 2, 3)
+// and DPS pass 1 (1, 2, 3):
+//   1. rows     a workgroup stages TR image rows of one plane in LDS, forming
+//               x0 = (x - k eps) / a (DPS) and zero-extending W -> Nw, runs an Nw-point FFT per
+//               row and stores the complex rows TRANSPOSED.  Only the H image rows are
+//               transformed: pad rows transform to zero and are never touched.
+//   2. columns  a workgroup loads TC columns (contiguous in the transposed intermediate),
+//               zero-extends H -> Nh, runs the forward Nh-point FFT, the pointwise step on the
+//               whole column (|z|; r = y - |z|, r^2 partial, u = grad_scale r z / |z|; or
+//               u = g z / |z|), the inverse Nh-point FFT in place, and stores rows
+//               pad_h .. pad_h + H - 1 back over the columns it loaded.  The Nh x Nw spectrum
+//               exists only in LDS.  apply stops after |z| and writes it to y.
+//   3. rows^-1  TR rows of the intermediate -> LDS, inverse Nw-point FFT, real part, columns
+//               pad_w .. pad_w + W - 1 -> v.
+//
+// Intermediate (the workspace): complex fp32 as (re, im) pairs, [sample][plane][Nw][H] — the
+// row FFT's output index kw is the slow axis, the image row h the fast one, so launch 2 reads
+// and writes each of its column tiles as ONE contiguous run of TC * H complex numbers.
+// 2 * batch * C * Nw * H floats, 8-byte aligned.
+//
+// FFT: Stockham autosort, decimation in time, between two LDS buffers (one barrier per pass):
+// radix-4 passes, one radix-2 pass when log2 is odd, and the radix-3 pass last, so every pass's
+// sub-transform length Ns is a power of two.  Pass with radix R on a line of N points, for
+// j < N / R, k = j mod Ns:
+//   v_i = in[j + i N / R] * w^(i k N / (Ns R)),  out[(j - k) R + k + i Ns] = DFT_R(v)_i
+// with w^q = exp(-2 pi i q / N) from an LDS table of N entries filled in the prologue by fp64
+// sincospi (correct to fp32 rounding; the inverse conjugates).  The "ortho" factors of both
+// axes, 1 / sqrt(Nh Nw), are applied once per transform in the pointwise step.
+//
+// LDS layout: a line of N complex numbers occupies NP = (N + N / 16) | 1 slots, element q at
+// q + (q >> 4).  Reads of a pass are consecutive per lane; the first radix-4 pass writes with a
+// stride of 4 complex numbers, which the pad every 16 spreads over all 32 banks of a 16-lane
+// ds_write_b64 group (the Ns = 4 pass keeps a 2-way conflict, later passes write runs of >= 16).
+// NP odd makes the transposing accesses (one lane per line) hit 32 distinct bank pairs.
+// Lines per workgroup: as many as fit 32000 bytes with both buffers and the table (so five
+// workgroups share a CU's 160 KiB), at most 16, at least 1 (Nh = 1024: one line, 25.6 KB).
+//
+// Every sample is computed alone: lines are assigned to workgroups by plane and tile only, the
+// r^2 partial of a (plane, column tile) is block_sum's fixed order over a fixed assignment of
+// elements to threads, so the bits do not depend on the batch, y_div or the shard.  No atomics.
+
+#include <algorithm>
+
+#define SP_TU 17  // debug-build site numbering (sp_common.h SP_DCHECK)
+#include "sp_common.h"
+
+namespace sp {
+
+// bytes of dynamic LDS a workgroup may take: five workgroups per CU.  Measured at B = 64,
+// 3 x 256^2 -> 384^2 (pass 1, us): 8 lines per workgroup (62 KB) 812, 7 lines 665, 5 lines 607,
+// 4 lines (29 KB) 573, 3 lines 605 - resident waves hide the barrier of every pass.
+constexpr int kPhaseLds = 32000;
+constexpr int kPhaseMaxLines = 16;
+
+enum { PH_APPLY = 0, PH_VJP = 1, PH_RESIDUAL = 2 };
+
+__host__ __device__ inline int phase_np(int N) { return (N + (N >> 4)) | 1; }
+__host__ __device__ inline int phase_slot(int q) { return q + (q >> 4); }
+
+// lines of an N-point transform per workgroup (a launch parameter, computed on the host)
+static inline int phase_lines(int N) {
+    int t = (kPhaseLds - 8 * N) / (16 * phase_np(N));
+    if (t > kPhaseMaxLines) t = kPhaseMaxLines;
+    return t < 1 ? 1 : t;
+}
+
+static inline int phase_lds_bytes(int N) { return 8 * N + 16 * phase_lines(N) * phase_np(N); }
+
+bool phase_size_ok(int N) {
+    if (N < 8 || N > 1024) return false;
+    while (N % 2 == 0) N /= 2;
+    return N == 1 || N == 3;
+}
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 w) {
+    return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
+}
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// tw[q] = exp(-2 pi i q / N), q < N
+__device__ __forceinline__ void phase_twiddles(float2* tw, int N) {
+    for (int q = threadIdx.x; q < N; q += kBlock) {
+        double s, c;
+        sincospi(-2.0 * (double)q / (double)N, &s, &c);
+        tw[q] = make_float2((float)c, (float)s);
+    }
+}
+
+// one Stockham pass of radix R over T lines (file comment); Ns is a power of two
+template <int R>
+__device__ __forceinline__ void phase_pass(const float2* __restrict__ in, float2* __restrict__ out,
+                                           const float2* __restrict__ tw, int N, int NP, int T,
+                                           int Ns, bool inverse) {
+    const int M = N / R, total = T * M, step = N / (Ns * R);
+    const int dq = kBlock / M, dr = kBlock - dq * M;
+    int t = static_cast<int>(threadIdx.x) / M, j = static_cast<int>(threadIdx.x) - t * M;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        SP_DCHECK(t < T && j < M && t * M + j == idx);
+        const int k = j & (Ns - 1);
+        const float2* li = in + t * NP;
+        float2 v[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) v[i] = li[phase_slot(j + i * M)];
+        if (Ns > 1) {  // the first pass has k = 0: every twiddle is 1
+#pragma unroll
+            for (int i = 1; i < R; ++i) {
+                SP_DCHECK(i * k * step < N);
+                float2 w = tw[i * k * step];
+                if (inverse) w.y = -w.y;
+                v[i] = cmul(v[i], w);
+            }
+        }
+        float2 o[R];
+        if constexpr (R == 2) {
+            o[0] = cadd(v[0], v[1]);
+            o[1] = csub(v[0], v[1]);
+        } else if constexpr (R == 4) {
+            const float2 a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]);
+            const float2 d = csub(v[1], v[3]);
+            const float2 a3 = inverse ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);  // +-i d
+            o[0] = cadd(a0, a2);
+            o[1] = cadd(a1, a3);
+            o[2] = csub(a0, a2);
+            o[3] = csub(a1, a3);
+        } else {
+            constexpr float c = 0.86602540378443864676f;  // sqrt(3) / 2
+            const float2 s = cadd(v[1], v[2]), d = csub(v[1], v[2]);
+            const float2 m = make_float2(v[0].x - 0.5f * s.x, v[0].y - 0.5f * s.y);
+            const float2 e = inverse ? make_float2(-c * d.y, c * d.x) : make_float2(c * d.y, -c * d.x);
+            o[0] = cadd(v[0], s);
+            o[1] = cadd(m, e);
+            o[2] = csub(m, e);
+        }
+        const int j0 = (j - k) * R + k;
+        float2* lo = out + t * NP;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            SP_DCHECK(j0 + i * Ns < N && phase_slot(j0 + i * Ns) < NP);
+            lo[phase_slot(j0 + i * Ns)] = o[i];
+        }
+        t += dq, j += dr;
+        if (j >= M) j -= M, ++t;
+    }
+    __syncthreads();
+}
+
+// N-point transforms of the T lines in `a` (natural order in, natural order out); returns the
+// buffer that holds the result.  The caller has synchronised after filling `a` and `tw`.
+__device__ __forceinline__ float2* phase_fft(float2* a, float2* b, const float2* tw, int N, int NP,
+                                             int T, bool inverse) {
+    const bool three = N % 3 == 0;
+    const int pow2 = three ? N / 3 : N;
+    int Ns = 1;
+    while (Ns < pow2) {
+        if ((pow2 / Ns) % 4 == 0) {
+            phase_pass<4>(a, b, tw, N, NP, T, Ns, inverse);
+            Ns *= 4;
+        } else {
+            phase_pass<2>(a, b, tw, N, NP, T, Ns, inverse);
+            Ns *= 2;
+        }
+        float2* s = a;
+        a = b, b = s;
+    }
+    if (three) {
+        phase_pass<3>(a, b, tw, N, NP, T, Ns, inverse);
+        a = b;
+    }
+    return a;
+}
+
+struct phase_geom {
+    int C, H, W, ph, pw, Nh, Nw;
+    __host__ __device__ explicit phase_geom(const sp_op& op)
+        : C(op.channels), H(op.height), W(op.width), ph(op.radius), pw(op.factor),
+          Nh(op.height + 2 * op.radius), Nw(op.width + 2 * op.factor) {}
+};
+
+// launch 1.  X0: x0 = (in - k eps) / a while staging, else x0 = in.
+template <bool X0>
+__global__ __launch_bounds__(kBlock) void k_phase_rows(sp_op op, const float* __restrict__ in,
+                                                       const float* __restrict__ eps, float a,
+                                                       float k, float2* __restrict__ ws, int T,
+                                                       const sp_step_rec* __restrict__ sched,
+                                                       const int32_t* __restrict__ cursor) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (X0 && sched) {  // device-resident schedule (graph replay)
+        const sp_dps_coefs& cf = sched[*cursor].c;
+        a = cf.a, k = cf.k;
+    }
+    const phase_geom g(op);
+    const int N = g.Nw, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.H + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int h0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    SP_DCHECK(c < g.C && h0 < g.H);
+    const float* __restrict__ ip = in + plane * g.H * g.W;
+    const float* __restrict__ ep = X0 ? eps + plane * g.H * g.W : nullptr;
+
+    phase_twiddles(tw, N);
+    for (int t = 0; t < T; ++t) {
+        const int h = h0 + t;
+        for (int q = threadIdx.x; q < N; q += kBlock) {
+            float val = 0.f;
+            const int j = q - g.pw;
+            if (h < g.H && j >= 0 && j < g.W) {
+                SP_DCHECK(h * g.W + j < g.H * g.W);
+                val = ip[h * g.W + j];
+                if constexpr (X0) val = (val - k * ep[h * g.W + j]) / a;
+            }
+            A[t * NP + phase_slot(q)] = make_float2(val, 0.f);
+        }
+    }
+    __syncthreads();
+    const float2* res = phase_fft(A, B, tw, N, NP, T, false);
+    // transposed store: ws[plane][kw][h], the tile's rows adjacent
+    float2* __restrict__ wp = ws + plane * (int64_t)N * g.H;
+    const int total = T * N;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, h = h0 + t;
+        if (h < g.H) {
+            SP_DCHECK(kw < N && kw * g.H + h < N * g.H);
+            wp[kw * g.H + h] = res[t * NP + phase_slot(kw)];
+        }
+    }
+}
+
+// launch 2
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_phase_cols(sp_op op, float2* __restrict__ ws,
+                                                       const float* __restrict__ yg, int64_t y_div,
+                                                       float gs, float* __restrict__ yout,
+                                                       float* __restrict__ partial, int P, int T,
+                                                       const sp_step_rec* __restrict__ sched,
+                                                       const int32_t* __restrict__ cursor) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[4];
+    if (MODE == PH_RESIDUAL && sched) gs = sched[*cursor].c.grad_scale;
+    const phase_geom g(op);
+    const int N = g.Nh, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.Nw + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int kw0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t b = blockIdx.y;
+    const int64_t plane = b * g.C + c;
+    SP_DCHECK(c < g.C && kw0 < g.Nw && (MODE != PH_RESIDUAL || static_cast<int>(blockIdx.x) < P));
+    float2* __restrict__ wp = ws + (plane * g.Nw + kw0) * (int64_t)g.H;  // the tile's columns
+    const int lines = min(T, g.Nw - kw0);
+
+    phase_twiddles(tw, N);
+    for (int t = 0; t < T; ++t)
+        for (int q = threadIdx.x; q < N; q += kBlock) {
+            float2 val = make_float2(0.f, 0.f);
+            const int h = q - g.ph;
+            if (t < lines && h >= 0 && h < g.H) val = wp[t * g.H + h];
+            A[t * NP + phase_slot(q)] = val;
+        }
+    __syncthreads();
+    float2* z = phase_fft(A, B, tw, N, NP, T, false);
+
+    // pointwise step over the whole columns: the tile's columns adjacent (y is row-major)
+    const float s = 1.f / sqrtf((float)g.Nh * (float)g.Nw);  // "ortho", both axes
+    const int64_t yrow = MODE == PH_RESIDUAL ? b / y_div : b;
+    const int64_t yoff = (yrow * g.C + c) * (int64_t)g.Nh * g.Nw + kw0;
+    float racc = 0.f;
+    const int total = T * N;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kh = idx / T, t = idx - kh * T;
+        if (t >= lines) continue;
+        SP_DCHECK(kh < N && kw0 + t < g.Nw);
+        float2* zp = z + t * NP + phase_slot(kh);
+        const float2 zz = make_float2(zp->x * s, zp->y * s);
+        const float mag = sqrtf(zz.x * zz.x + zz.y * zz.y);
+        const int64_t yi = yoff + (int64_t)kh * g.Nw + t;
+        if constexpr (MODE == PH_APPLY) {
+            yout[yi] = mag;
+        } else {
+            float coef = yg[yi];  // VJP: the cotangent g
+            if constexpr (MODE == PH_RESIDUAL) {
+                const float r = coef - mag;
+                racc += r * r;
+                coef = gs * r;
+            }
+            // u = coef z / |z| (0 at |z| = 0), times the inverse transform's "ortho" factor
+            const float q = mag > 0.f ? coef * s / mag : 0.f;
+            *zp = make_float2(q * zz.x, q * zz.y);
+        }
+    }
+    if constexpr (MODE == PH_RESIDUAL) {
+        const float tsum = block_sum(racc, red);
+        if (threadIdx.x == 0) partial[b * P + blockIdx.x] = tsum;
+    }
+    if constexpr (MODE == PH_APPLY) return;
+    __syncthreads();
+    const float2* u = phase_fft(z, z == A ? B : A, tw, N, NP, T, true);
+    const int keep = lines * g.H;
+    for (int idx = threadIdx.x; idx < keep; idx += kBlock) {
+        const int t = idx / g.H, h = idx - t * g.H;
+        SP_DCHECK(t < lines && g.ph + h < N);
+        wp[idx] = u[t * NP + phase_slot(g.ph + h)];
+    }
+}
+
+// launch 3
+__global__ __launch_bounds__(kBlock) void k_phase_rows_inv(sp_op op, const float2* __restrict__ ws,
+                                                           float* __restrict__ out, int T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const phase_geom g(op);
+    const int N = g.Nw, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.H + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int h0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    SP_DCHECK(c < g.C && h0 < g.H);
+    const float2* __restrict__ wp = ws + plane * (int64_t)N * g.H;
+
+    phase_twiddles(tw, N);
+    const int total = T * N;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, h = h0 + t;
+        float2 val = make_float2(0.f, 0.f);
+        if (h < g.H) {
+            SP_DCHECK(kw * g.H + h < N * g.H);
+            val = wp[kw * g.H + h];
+        }
+        A[t * NP + phase_slot(kw)] = val;
+    }
+    __syncthreads();
+    const float2* res = phase_fft(A, B, tw, N, NP, T, true);
+    float* __restrict__ op_out = out + plane * g.H * g.W;
+    for (int t = 0; t < T; ++t) {
+        const int h = h0 + t;
+        if (h >= g.H) break;
+        for (int j = threadIdx.x; j < g.W; j += kBlock) {
+            SP_DCHECK(g.pw + j < N && h * g.W + j < g.H * g.W);
+            op_out[h * g.W + j] = res[t * NP + phase_slot(g.pw + j)].x;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side (called from the entry points in sp_dps.hip; `op` is valid)
+// ---------------------------------------------------------------------------
+static inline int phase_col_tiles(const sp_op* op) {
+    const phase_geom g(*op);
+    const int T = phase_lines(g.Nh);
+    return (g.Nw + T - 1) / T;
+}
+static inline int phase_row_tiles(const sp_op* op) {
+    const phase_geom g(*op);
+    const int T = phase_lines(g.Nw);
+    return (g.H + T - 1) / T;
+}
+
+// column tiles per sample = workgroups per sample of launch 2 = r^2 partials per sample
+int64_t phase_partials(const sp_op* op) { return (int64_t)op->channels * phase_col_tiles(op); }
+
+// floats of the intermediate
+int64_t phase_workspace(const sp_op* op, int64_t batch) {
+    const phase_geom g(*op);
+    return 2 * batch * g.C * (int64_t)g.Nw * g.H;
+}
+
+template <typename K, typename... Args>
+static inline void phase_launch(int kind, double work, K kernel, unsigned gx, int64_t batch, int N,
+                                hipStream_t s, Args... args) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (kind && timing_on()) timing_events(kind, work, &e0, &e1);
+    hipExtLaunchKernelGGL(kernel, dim3(gx, static_cast<unsigned>(batch)), dim3(kBlock),
+                          phase_lds_bytes(N), s, e0, e1, 0, args...);
+}
+
+int phase_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                hipStream_t s) {
+    const phase_geom g(*op);
+    float2* ws = reinterpret_cast<float2*>(work);
+    phase_launch(0, 0.0, k_phase_rows<false>, op->channels * phase_row_tiles(op), batch, g.Nw, s, *op,
+                 x, (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), (const sp_step_rec*)nullptr,
+                 (const int32_t*)nullptr);
+    int rc = check_launch("sp_op_apply_ws");
+    if (rc != SP_OK) return rc;
+    phase_launch(0, 0.0, k_phase_cols<PH_APPLY>, op->channels * phase_col_tiles(op), batch, g.Nh, s,
+                 *op, ws, (const float*)nullptr, (int64_t)1, 0.f, y, (float*)nullptr, 0, phase_lines(g.Nh),
+                 (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
+    return check_launch("sp_op_apply_ws");
+}
+
+int phase_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
+              float* work, hipStream_t s) {
+    const phase_geom g(*op);
+    float2* ws = reinterpret_cast<float2*>(work);
+    phase_launch(0, 0.0, k_phase_rows<false>, op->channels * phase_row_tiles(op), batch, g.Nw, s, *op,
+                 x, (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), (const sp_step_rec*)nullptr,
+                 (const int32_t*)nullptr);
+    int rc = check_launch("sp_op_vjp_ws");
+    if (rc != SP_OK) return rc;
+    phase_launch(0, 0.0, k_phase_cols<PH_VJP>, op->channels * phase_col_tiles(op), batch, g.Nh, s, *op,
+                 ws, gy, (int64_t)1, 0.f, (float*)nullptr, (float*)nullptr, 0, phase_lines(g.Nh),
+                 (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
+    rc = check_launch("sp_op_vjp_ws");
+    if (rc != SP_OK) return rc;
+    phase_launch(0, 0.0, k_phase_rows_inv, op->channels * phase_row_tiles(op), batch, g.Nw, s, *op,
+                 (const float2*)ws, dx, phase_lines(g.Nw));
+    return check_launch("sp_op_vjp_ws");
+}
+
+// rows (x, eps -> work), columns (work, y -> work, partials), rows^-1 (work -> v)
+int phase_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
+                       int64_t batch, int64_t y_div, float a, float k, float gs,
+                       const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
+                       float* partial, hipStream_t s) {
+    const phase_geom g(*op);
+    float2* ws = reinterpret_cast<float2*>(work);
+    const int P = static_cast<int>(phase_partials(op));
+    phase_launch(TK_DPS_RESIDUAL, (double)batch, k_phase_rows<true>, op->channels * phase_row_tiles(op),
+                 batch, g.Nw, s, *op, x, eps, a, k, ws, phase_lines(g.Nw), sched, cursor);
+    int rc = check_launch("sp_dps_residual_ws");
+    if (rc != SP_OK) return rc;
+    phase_launch(TK_DPS_RESIDUAL, 0.0, k_phase_cols<PH_RESIDUAL>, static_cast<unsigned>(P), batch, g.Nh,
+                 s, *op, ws, y, y_div, gs, (float*)nullptr, partial, P, phase_lines(g.Nh), sched, cursor);
+    rc = check_launch("sp_dps_residual_ws");
+    if (rc != SP_OK) return rc;
+    phase_launch(TK_DPS_RESIDUAL, 0.0, k_phase_rows_inv, op->channels * phase_row_tiles(op), batch, g.Nw,
+                 s, *op, (const float2*)ws, v, phase_lines(g.Nw));
+    return check_launch("sp_dps_residual_ws");
+}
+
+}  // namespace sp

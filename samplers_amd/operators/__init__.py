@@ -11,6 +11,7 @@ from .inpainting import (
     get_mask_random,
     get_mask_side_painting,
 )
+from .phase import PhaseRetrievalOperator
 from .linear import GeneralSVDOperator, LinearOperator, SVDOperator
 from .psf import MotionBlurOperator, PSFBlurOperator, motion_blur_kernel
 from .superres import SuperResolutionOperator
@@ -31,6 +32,7 @@ __all__ = [
     "SuperResolutionOperator",
     "PSFBlurOperator",
     "MotionBlurOperator",
+    "PhaseRetrievalOperator",
     "motion_blur_kernel",
     "get_mask_inpaint_center",
     "get_mask_side_painting",

@@ -26,6 +26,9 @@ class Operator(torch.nn.Module, ABC):
     # c in ∂/∂x̂₀ ‖A⁺y − A⁺A x̂₀‖² = −c·Aᵀ(y − A x̂₀) for natively implemented operators with a
     # pseudo-inverse (the fused PGDM step): 2 for partial isometries (A⁺ = Aᵀ).
     pinv_grad_scale: float = 2.0
+    # True when a HIP descriptor's sp_op_apply / sp_op_adjoint routes apply (every natively
+    # implemented linear operator); a nonlinear native operator sets it False
+    hip_linear: bool = True
 
     def __init__(self, x_shape: Shape, device: Device = None) -> None:
         super().__init__()

@@ -130,7 +130,8 @@ class FusedDPSStep:
             raise NotImplementedError(
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
-                "GaussianBlurOperator, SuperResolutionOperator and PSFBlurOperator (and subclasses)"
+                "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses) and "
+                "PhaseRetrievalOperator"
             )
         _hip.require_cuda(observation_rows, "DPSSampler")
         if observation_rows.dtype != torch.float32:
@@ -148,6 +149,9 @@ class FusedDPSStep:
             raise _hip.HipLibraryError(f"operator descriptor rejected ({self.partials})")
         if mode not in ("dps", "pgdm"):
             raise ValueError(mode)
+        if mode == "pgdm" and desc.kind == _hip.SP_OP_PHASE:
+            raise NotImplementedError(f"{type(op).__name__} is nonlinear and has no "
+                                      "apply_pseudo_inverse: PGDM does not apply")
         self.mode = mode
         # DPS: d log p/d(Ax) = c r.  PGDM: d/dx0 of ||A^+ y - A^+ A x0||^2 = -c A^T r with the
         # operator's pinv_grad_scale c: 2 for the partial isometries (A^+ = A^T: identity,
@@ -170,8 +174,10 @@ class FusedDPSStep:
         # sample; with non-temporal loads and 2 float4 groups per thread it is 7 % faster than
         # re-reading pass 1's v, 42.3 vs 45.2 us at B = 64, 256^2) or re-reads v (reuse_v).
         # Blur always re-reads it (its adjoint needs a halo), and so does super-resolution (v is
-        # constant over a block; pass 2 stays the flat identity-kind kernel) and the PSF blur.
-        self.needs_v = desc.kind in (_hip.SP_OP_BLUR, _hip.SP_OP_SR, _hip.SP_OP_PSF) or bool(reuse_v)
+        # constant over a block; pass 2 stays the flat identity-kind kernel), the PSF blur and phase
+        # retrieval (v = J^T(grad_scale r) comes out of its FFT passes).
+        self.needs_v = desc.kind in (_hip.SP_OP_BLUR, _hip.SP_OP_SR, _hip.SP_OP_PSF,
+                                     _hip.SP_OP_PHASE) or bool(reuse_v)
         self.micro_batch = micro_batch
         self.timer = timer
 
@@ -188,7 +194,7 @@ class FusedDPSStep:
         """Pass 1's work buffer for ``batch`` samples (``sp_dps_workspace`` floats; None where
         the operator's pass needs none).  Allocated by torch on the launch stream, so a graph
         capture records it like every other buffer of the step."""
-        if self.desc.kind != _hip.SP_OP_PSF:  # one-pass kinds: no host call in the step loop
+        if self.desc.kind not in (_hip.SP_OP_PSF, _hip.SP_OP_PHASE):  # one-pass kinds: no host call in the step loop
             return None
         floats = int(self.lib.sp_dps_workspace(self.desc, batch))
         if floats < 0:

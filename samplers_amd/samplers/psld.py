@@ -71,6 +71,8 @@ class FusedPSLDStep:
                  omega: float = 0.1, eta: float = 1.0, group=None) -> None:
         op = inverse_problem.operator
         desc = getattr(op, "hip_descriptor", lambda: None)()
+        if not getattr(op, "hip_linear", True):  # nonlinear native operator: the generic route,
+            desc = None                          # which needs (and fails at) apply_transpose
         _hip.require_cuda(observation_rows, "PSLDSampler")
         self.lib = _hip.load_library()
         self.net, self.op, self.desc = network, op, desc
