@@ -184,6 +184,17 @@ int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
  * of sp_dps_workspace for PHASE.  SP_EINVAL for a rejected descriptor or batch <= 0. */
 int64_t sp_op_workspace(const sp_op* op, int64_t batch);
 
+/* What the kind of `op` does at the entry points below, as bits; 0 for a rejected descriptor.
+ * A caller branches on these instead of listing kinds (no reference counterpart). */
+enum {
+    SP_TRAIT_UPDATE_READS_V = 1, /* sp_dps_update requires v (it cannot re-derive it)          */
+    SP_TRAIT_DPS_WORKSPACE = 2,  /* sp_dps_workspace > 0: pass 1 runs in the _ws forms only    */
+    SP_TRAIT_FUSED_LATENT = 4,   /* sp_psld_pixel and sp_pixel_opt_step exist for the kind     */
+    SP_TRAIT_LINEAR = 8,         /* sp_op_apply / sp_op_adjoint exist (else _apply_ws/_vjp_ws) */
+    SP_TRAIT_NEEDS_ATA_U = 16    /* sp_psld_cotangent requires ata_u                           */
+};
+uint32_t sp_op_traits(const sp_op* op);
+
 /* DPS pass 1 — replaces dps.py:99-103 up to the prior's VJP and dps.py:117-118:
  *   x0  = (x - k*eps)/a                         (networks/base.py:41-43)
  *   r   = y - A(x0)                             (inverse_problem.py:17-18)

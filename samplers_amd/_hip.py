@@ -19,9 +19,9 @@ DEBUG_LIB_PATH = Path(__file__).resolve().parent / "lib" / "debug" / "libsampler
 
 SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR, SP_OP_PSF = 0, 1, 2, 3, 4, 5
 SP_OP_PHASE = 6  # nonlinear: sp_op_apply_ws / sp_op_vjp_ws, no adjoint
-# kinds whose adjoint needs a halo: no fused PSLD / pixel-optimisation pass, the samplers compose
-# them from sp_op_apply / sp_op_adjoint
-HALO_KINDS = (SP_OP_BLUR, SP_OP_PSF)
+# sp_op_traits bits: what a kind does at the entry points (the library's table, not a list here)
+SP_TRAIT_UPDATE_READS_V, SP_TRAIT_DPS_WORKSPACE, SP_TRAIT_FUSED_LATENT = 1, 2, 4
+SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U = 8, 16
 
 _ERRORS = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported"}
 
@@ -106,6 +106,7 @@ SIGNATURES = {
     "sp_op_apply": (ctypes.c_int, [_OPP, _P, _P, _I64, _P]),
     "sp_op_adjoint": (ctypes.c_int, [_OPP, _P, _P, _I64, _P]),
     "sp_op_workspace": (_I64, [_OPP, _I64]),
+    "sp_op_traits": (ctypes.c_uint32, [_OPP]),
     "sp_op_apply_ws": (ctypes.c_int, [_OPP, _P, _P, _I64, _P, _P]),
     "sp_op_vjp_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _P, _P]),
     "sp_residual_grad": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P]),

@@ -25,7 +25,7 @@
 #include <utility>
 
 #define SP_TU 2  // debug-build site numbering (sp_common.h SP_DCHECK)
-#include "sp_common.h"
+#include "sp_ops.h"
 
 namespace sp {
 
@@ -1000,6 +1000,12 @@ __global__ __launch_bounds__(64 * G, 2) void k_blur_dps_reg(
     if (lane == 0) partial[(int64_t)b * P + c * nseg + sg] = t;
 }
 
+bool blur_valid(const sp_op* op) {
+    return op->taps && op->radius >= 1 && op->radius <= 8 && op->m == op->n &&
+           (int64_t)op->channels * op->height * op->width == op->n &&
+           op->height > 2 * op->radius && op->width > 2 * op->radius;
+}
+
 int64_t blur_partials(const sp_op* op) {
     if (blur_streams(op)) return (int64_t)op->channels * (op->height / SSEG);
     const int64_t tiles = (int64_t)((op->height + TH - 1) / TH) * ((op->width + TW - 1) / TW);
@@ -1065,12 +1071,9 @@ static int launch_blur(const sp_op* op, const float* in, const float* eps, const
     return check_launch("blur");
 }
 
-int blur_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                      int64_t batch, int64_t y_div, float a, float k, float gs,
-                      const sp_step_rec* sched, const int32_t* cursor, float* v, float* partial,
-                      hipStream_t s) {
-    return launch_blur<MODE_DPS>(op, x, eps, y, y_div, a, k, gs, v, partial, batch, s, sched,
-                                 cursor);
+int blur_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    return launch_blur<MODE_DPS>(op, r.x, r.eps, r.y, r.y_div, r.a, r.k, r.gs, r.v, r.partial, r.batch,
+                                 s, r.sched, r.cursor);
 }
 
 int blur_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s) {

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/samplers_hip.h"
 
 namespace sp {
@@ -263,16 +265,33 @@ enum {
 };
 
 template <typename K, typename... Args>
-inline void launch_w(int kind, double work, K kernel, dim3 grid, dim3 block, hipStream_t s,
-                     Args... args) {
+inline void launch_w(int kind, double work, K kernel, dim3 grid, dim3 block, size_t lds_bytes,
+                     hipStream_t s, Args... args) {  // lds_bytes of dynamic LDS
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (kind && timing_on()) timing_events(kind, work, &e0, &e1);
-    hipExtLaunchKernelGGL(kernel, grid, block, 0, s, e0, e1, 0, args...);
+    hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, s, e0, e1, 0, args...);
+}
+
+template <typename K, typename... Args>
+inline void launch_w(int kind, double work, K kernel, dim3 grid, dim3 block, hipStream_t s,
+                     Args... args) {
+    launch_w(kind, work, kernel, grid, block, size_t(0), s, args...);
 }
 
 template <typename K, typename... Args>
 inline void launch(int kind, K kernel, dim3 grid, dim3 block, hipStream_t s, Args... args) {
     launch_w(kind, 0.0, kernel, grid, block, s, args...);
+}
+
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// gx workgroups per sample, one grid row per sample
+inline dim3 sample_grid(int64_t gx, int64_t batch) { return dim3((unsigned)gx, (unsigned)batch); }
+
+// grid.x for grid-stride kernels: enough blocks to fill 256 CUs a few times over
+inline unsigned stride_blocks(int64_t work, int V, int64_t batch) {
+    const int64_t cap = std::max<int64_t>(1, 4096 / std::max<int64_t>(batch, 1));
+    return static_cast<unsigned>(std::max<int64_t>(1, std::min(cdiv(work, (int64_t)kBlock * V), cap)));
 }
 
 }  // namespace sp

@@ -16,7 +16,7 @@
 #include <vector>
 
 #define SP_TU 1  // debug-build site numbering (sp_common.h SP_DCHECK)
-#include "sp_common.h"
+#include "sp_ops.h"
 
 namespace sp {
 
@@ -382,93 +382,96 @@ __global__ __launch_bounds__(kBlock) void k_mask(sp_op op, const float* __restri
     }
 }
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// grid.x for grid-stride kernels: enough blocks to fill 256 CUs a few times over
-static inline unsigned stride_blocks(int64_t work, int V, int64_t batch) {
-    int64_t blocks = cdiv(work, (int64_t)kBlock * V);
-    const int64_t cap = std::max<int64_t>(1, 4096 / std::max<int64_t>(batch, 1));
-    if (blocks > cap) blocks = cap;
-    return static_cast<unsigned>(std::max<int64_t>(blocks, 1));
-}
-
 int64_t tiles_elementwise(int64_t n) {
     const int V = (n % 4 == 0) ? 4 : 1;
     return cdiv(n, (int64_t)kIter * kBlock * V);
 }
 
-bool phase_size_ok(int N);  // sp_phase.hip: 2^k or 3 * 2^k in [8, 1024]
+// IDENTITY / INPAINT / MASK: one set of row functions (the latent passes: sp_latent.hip)
+static bool identity_valid(const sp_op* op) { return op->m == op->n; }
+static bool inpaint_valid(const sp_op* op) { return op->keep_bits && op->word_rank && op->m <= op->n; }
+static bool mask_valid(const sp_op* op) { return op->keep_bits && op->m == op->n; }
 
-bool valid_op(const sp_op* op) {
-    if (!op || op->n <= 0 || op->m <= 0) return false;
+static int64_t elementwise_partials(const sp_op* op) { return tiles_elementwise(op->n); }
+
+static int elementwise_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    const int P = static_cast<int>(tiles_elementwise(op->n));
+    const dim3 grid(P, static_cast<unsigned>(r.batch));
+    const bool v4 = op->n % 4 == 0;
+#define SP_K1(OPK, V)                                                                       \
+    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_dps_residual<OPK, V>, grid, dim3(kBlock), s, *op, r.x, r.eps, r.y, \
+           r.y_div, r.a, r.k, r.gs, r.v, r.partial, P, r.sched, r.cursor)
     switch (op->kind) {
-        case SP_OP_IDENTITY: return op->m == op->n;
-        case SP_OP_INPAINT: return op->keep_bits && op->word_rank && op->m <= op->n;
-        case SP_OP_MASK: return op->keep_bits && op->m == op->n;
-        case SP_OP_BLUR:
-            return op->taps && op->radius >= 1 && op->radius <= 8 && op->m == op->n &&
-                   (int64_t)op->channels * op->height * op->width == op->n &&
-                   op->height > 2 * op->radius && op->width > 2 * op->radius;
-        case SP_OP_SR:
-            return (op->factor == 2 || op->factor == 4 || op->factor == 8) && op->channels > 0 &&
-                   op->height > 0 && op->width > 0 &&
-                   (int64_t)op->channels * op->height * op->width == op->n &&
-                   op->height % op->factor == 0 && op->width % op->factor == 0 &&
-                   op->m * op->factor * op->factor == op->n;
-        case SP_OP_PSF:
-            return op->taps && op->radius >= 1 && op->radius <= 30 && op->m == op->n &&
-                   op->channels > 0 && (int64_t)op->channels * op->height * op->width == op->n &&
-                   op->height > 2 * op->radius && op->width > 2 * op->radius;
-        case SP_OP_PHASE:  // radius = pad_h, factor = pad_w
-            return !op->taps && !op->keep_bits && !op->word_rank && op->radius >= 0 &&
-                   op->factor >= 0 && op->channels > 0 && op->height > 0 && op->width > 0 &&
-                   op->height <= 1024 && op->width <= 1024 && op->radius <= 512 && op->factor <= 512 &&
-                   phase_size_ok(op->height + 2 * op->radius) &&
-                   phase_size_ok(op->width + 2 * op->factor) &&
-                   (int64_t)op->channels * op->height * op->width == op->n &&
-                   (int64_t)op->channels * (op->height + 2 * op->radius) *
-                           (op->width + 2 * op->factor) == op->m;
-        default: return false;
+        case SP_OP_IDENTITY: if (v4) SP_K1(SP_OP_IDENTITY, 4); else SP_K1(SP_OP_IDENTITY, 1); break;
+        case SP_OP_MASK: if (v4) SP_K1(SP_OP_MASK, 4); else SP_K1(SP_OP_MASK, 1); break;
+        default: if (v4) SP_K1(SP_OP_INPAINT, 4); else SP_K1(SP_OP_INPAINT, 1); break;
     }
+#undef SP_K1
+    return check_launch("sp_dps_residual");
 }
 
-// blur entry points (sp_blur.hip)
-int64_t blur_partials(const sp_op* op);
-int blur_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                      int64_t batch, int64_t y_div, float a, float k, float gs,
-                      const sp_step_rec* sched, const int32_t* cursor, float* v, float* partial,
-                      hipStream_t s);
-int blur_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
-int blur_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
+// y = A x, or x = A^T y: a copy, the mask (self-adjoint), the gather or its scatter
+template <bool ADJOINT>
+static int elementwise_map(const sp_op* op, const float* in, float* out, int64_t batch, hipStream_t s) {
+    const char* what = ADJOINT ? "sp_op_adjoint" : "sp_op_apply";
+    if (op->kind == SP_OP_IDENTITY) {
+        const hipError_t e = hipMemcpyAsync(out, in, sizeof(float) * op->n * batch,
+                                            hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { set_error(what, e); return SP_ELAUNCH; }
+        return SP_OK;
+    }
+    const bool v4 = op->n % 4 == 0;
+    const dim3 grid(stride_blocks(op->n, v4 ? 4 : 1, batch), batch);
+#define SP_MAP(KERNEL)                                                                \
+    if (v4) hipLaunchKernelGGL(KERNEL<4>, grid, dim3(kBlock), 0, s, *op, in, out);    \
+    else hipLaunchKernelGGL(KERNEL<1>, grid, dim3(kBlock), 0, s, *op, in, out)
+    if (op->kind == SP_OP_MASK) { SP_MAP(k_mask); }
+    else if (ADJOINT) { SP_MAP(k_inpaint_scatter); }
+    else { SP_MAP(k_inpaint_gather); }
+#undef SP_MAP
+    return check_launch(what);
+}
 
-// super-resolution entry points (sp_sr.hip)
-int64_t sr_partials(const sp_op* op);
-int sr_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                    int64_t batch, int64_t y_div, float a, float k, float gs,
-                    const sp_step_rec* sched, const int32_t* cursor, float* v, float* partial,
-                    hipStream_t s);
-int sr_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
-int sr_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
+// The dispatch table: one row per kind, indexed by sp_op.kind (sp_ops.h)
+#define SP_ELEMENTWISE_ROW(VALID)                                                              \
+    {VALID, elementwise_partials, nullptr, nullptr, elementwise_dps_residual,                  \
+     elementwise_map<false>, elementwise_map<true>, nullptr, nullptr, elementwise_psld_pixel,  \
+     elementwise_psld_cotangent, elementwise_pixel_opt, SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR}
+static const op_kind g_kinds[] = {
+    /* SP_OP_IDENTITY */ SP_ELEMENTWISE_ROW(identity_valid),
+    /* SP_OP_INPAINT */ SP_ELEMENTWISE_ROW(inpaint_valid),
+    /* SP_OP_BLUR: no fused latent pass (its adjoint needs a halo), A^T A u from the caller */
+    {blur_valid, blur_partials, nullptr, nullptr, blur_dps_residual, blur_apply, blur_adjoint,
+     nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
+    /* SP_OP_MASK */ SP_ELEMENTWISE_ROW(mask_valid),
+    /* SP_OP_SR */
+    {sr_valid, sr_partials, nullptr, nullptr, sr_dps_residual, sr_apply, sr_adjoint, nullptr,
+     nullptr, sr_psld_pixel, sr_psld_cotangent, sr_pixel_opt,
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR},
+    /* SP_OP_PSF: as BLUR, and two launches through the caller's work buffer (_ws forms) */
+    {psf_valid, psf_partials, psf_workspace, nullptr, psf_dps_residual, psf_apply, psf_adjoint,
+     nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
+    /* SP_OP_PHASE: nonlinear (no adjoint, no A^T A, no PSLD), three launches through work */
+    {phase_valid, phase_partials, phase_workspace, phase_workspace, phase_dps_residual, nullptr,
+     nullptr, phase_apply, phase_vjp, nullptr, nullptr, nullptr,
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
+};
+#undef SP_ELEMENTWISE_ROW
+constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
+static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
+                  SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && kKinds == 7,
+              "g_kinds rows follow the sp_op kind numbering");
 
-// point-spread-function blur entry points (sp_psf.hip)
-int64_t psf_partials(const sp_op* op);
-int psf_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                     int64_t batch, int64_t y_div, float a, float k, float gs,
-                     const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
-                     float* partial, hipStream_t s);
-int psf_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s);
-int psf_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s);
+const op_kind* kind_of(const sp_op* op) {
+    return op && op->kind >= 0 && op->kind < kKinds ? &g_kinds[op->kind] : nullptr;
+}
 
-// Fourier phase retrieval entry points (sp_phase.hip)
-int64_t phase_partials(const sp_op* op);
-int64_t phase_workspace(const sp_op* op, int64_t batch);
-int phase_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                       int64_t batch, int64_t y_div, float a, float k, float gs,
-                       const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
-                       float* partial, hipStream_t s);
-int phase_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work, hipStream_t s);
-int phase_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
-              float* work, hipStream_t s);
+bool valid_op(const sp_op* op) {
+    const op_kind* k = kind_of(op);
+    return k && op->n > 0 && op->m > 0 && k->valid(op);
+}
 
 }  // namespace sp
 
@@ -476,7 +479,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 104; }
+int sp_version(void) { return 105; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -539,85 +542,50 @@ int sp_timing_collect_work(int32_t* kinds, float* ms, double* work, int max_reco
 
 const char* sp_last_error(void) { return g_err; }
 
-int64_t sp_rsq_partials(const sp_op* op) {
-    if (!valid_op(op)) return SP_EINVAL;
-    if (op->kind == SP_OP_BLUR) return blur_partials(op);
-    if (op->kind == SP_OP_SR) return sr_partials(op);
-    if (op->kind == SP_OP_PSF) return psf_partials(op);
-    if (op->kind == SP_OP_PHASE) return phase_partials(op);
-    return tiles_elementwise(op->n);
-}
+uint32_t sp_op_traits(const sp_op* op) { return valid_op(op) ? kind_of(op)->traits : 0; }
+
+int64_t sp_rsq_partials(const sp_op* op) { return valid_op(op) ? kind_of(op)->partials(op) : SP_EINVAL; }
 
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch) {
     if (!valid_op(op) || batch <= 0) return SP_EINVAL;
-    if (op->kind == SP_OP_PHASE) return phase_workspace(op, batch);
-    return op->kind == SP_OP_PSF ? batch * op->m : 0;
+    const op_kind* k = kind_of(op);
+    return k->dps_workspace ? k->dps_workspace(op, batch) : 0;
 }
 
 int64_t sp_op_workspace(const sp_op* op, int64_t batch) {
     if (!valid_op(op) || batch <= 0) return SP_EINVAL;
-    return op->kind == SP_OP_PHASE ? phase_workspace(op, batch) : 0;
+    const op_kind* k = kind_of(op);
+    return k->op_workspace ? k->op_workspace(op, batch) : 0;
 }
 
 int64_t sp_vec_partials(int64_t count) { return count > 0 ? tiles_elementwise(count) : SP_EINVAL; }
 
-static int dps_residual_impl(const sp_op* op, const float* x, const float* eps, const float* y,
-                             int64_t batch, int64_t y_div, sp_dps_coefs c,
-                             const sp_step_rec* sched, const int32_t* cursor, float* v_out,
-                             float* rsq_partial, bool ws, float* work, sp_stream_t stream) {
-    if (!valid_op(op) || !x || !eps || !y || !v_out || !rsq_partial || batch <= 0 ||
-        y_div <= 0 || batch > 65535)
+static int dps_residual_impl(const sp_op* op, const dps_residual_args& r, bool ws, sp_stream_t stream) {
+    if (!valid_op(op) || !r.x || !r.eps || !r.y || !r.v || !r.partial || r.batch <= 0 || r.y_div <= 0 ||
+        r.batch > 65535)
         return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (op->kind == SP_OP_PSF) {  // two launches through the caller's work buffer (_ws forms)
-        if (!ws) return SP_EUNSUPPORTED;
-        if (!work) return SP_EINVAL;
-        return psf_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
-                                v_out, work, rsq_partial, s);
+    const op_kind* kind = kind_of(op);
+    if (kind->traits & SP_TRAIT_DPS_WORKSPACE) {  // several launches through the caller's work buffer
+        if (!ws) return SP_EUNSUPPORTED;  // an entry without a work argument
+        if (!r.work) return SP_EINVAL;
     }
-    if (op->kind == SP_OP_PHASE) {  // three launches through the work buffer (_ws forms)
-        if (!ws) return SP_EUNSUPPORTED;
-        if (!work) return SP_EINVAL;
-        return phase_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
-                                  v_out, work, rsq_partial, s);
-    }
-    if (op->kind == SP_OP_BLUR)
-        return blur_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched,
-                                 cursor, v_out, rsq_partial, s);
-    if (op->kind == SP_OP_SR)
-        return sr_dps_residual(op, x, eps, y, batch, y_div, c.a, c.k, c.grad_scale, sched, cursor,
-                               v_out, rsq_partial, s);
-    const int P = static_cast<int>(tiles_elementwise(op->n));
-    const dim3 grid(P, static_cast<unsigned>(batch));
-    const bool v4 = op->n % 4 == 0;
-#define SP_K1(OPK, V)                                                                       \
-    launch_w(TK_DPS_RESIDUAL, (double)batch, k_dps_residual<OPK, V>, grid, dim3(kBlock), s, *op, x, eps, y, y_div, \
-           c.a, c.k, c.grad_scale, v_out, rsq_partial, P, sched, cursor)
-    if (op->kind == SP_OP_IDENTITY) {
-        if (v4) SP_K1(SP_OP_IDENTITY, 4); else SP_K1(SP_OP_IDENTITY, 1);
-    } else if (op->kind == SP_OP_MASK) {
-        if (v4) SP_K1(SP_OP_MASK, 4); else SP_K1(SP_OP_MASK, 1);
-    } else {
-        if (v4) SP_K1(SP_OP_INPAINT, 4); else SP_K1(SP_OP_INPAINT, 1);
-    }
-#undef SP_K1
-    return check_launch("sp_dps_residual");
+    return kind->dps_residual(op, r, static_cast<hipStream_t>(stream));
 }
 
 int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
                     int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
                     float* rsq_partial, sp_stream_t stream) {
     if (!c) return SP_EINVAL;
-    return dps_residual_impl(op, x, eps, y, batch, y_div, *c, nullptr, nullptr, v_out, rsq_partial,
-                             false, nullptr, stream);
+    return dps_residual_impl(op, {x, eps, y, batch, y_div, c->a, c->k, c->grad_scale, nullptr, nullptr,
+                                  v_out, rsq_partial, nullptr}, false, stream);
 }
 
 int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
                        int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
                        float* rsq_partial, float* work, sp_stream_t stream) {
     if (!c) return SP_EINVAL;
-    return dps_residual_impl(op, x, eps, y, batch, y_div, *c, nullptr, nullptr, v_out, rsq_partial,
-                             true, work, stream);
+    return dps_residual_impl(op, {x, eps, y, batch, y_div, c->a, c->k, c->grad_scale, nullptr, nullptr,
+                                  v_out, rsq_partial, work}, true, stream);
 }
 
 int sp_dps_residual_sched(const sp_op* op, const float* x, const float* eps, const float* y,
@@ -625,8 +593,8 @@ int sp_dps_residual_sched(const sp_op* op, const float* x, const float* eps, con
                           const int32_t* cursor, float* v_out, float* rsq_partial,
                           sp_stream_t stream) {
     if (!sched || !cursor) return SP_EINVAL;
-    return dps_residual_impl(op, x, eps, y, batch, y_div, sp_dps_coefs{}, sched, cursor, v_out,
-                             rsq_partial, false, nullptr, stream);
+    return dps_residual_impl(op, {x, eps, y, batch, y_div, 0.f, 0.f, 0.f, sched, cursor, v_out,
+                                  rsq_partial, nullptr}, false, stream);
 }
 
 int sp_dps_residual_sched_ws(const sp_op* op, const float* x, const float* eps, const float* y,
@@ -634,8 +602,8 @@ int sp_dps_residual_sched_ws(const sp_op* op, const float* x, const float* eps, 
                              const int32_t* cursor, float* v_out, float* rsq_partial, float* work,
                              sp_stream_t stream) {
     if (!sched || !cursor) return SP_EINVAL;
-    return dps_residual_impl(op, x, eps, y, batch, y_div, sp_dps_coefs{}, sched, cursor, v_out,
-                             rsq_partial, true, work, stream);
+    return dps_residual_impl(op, {x, eps, y, batch, y_div, 0.f, 0.f, 0.f, sched, cursor, v_out,
+                                  rsq_partial, work}, true, stream);
 }
 
 static int dps_update_impl(const sp_op* op, const float* x, const float* eps, const float* y,
@@ -647,15 +615,14 @@ static int dps_update_impl(const sp_op* op, const float* x, const float* eps, co
     if (!valid_op(op) || !x || !eps || !w || !x_out || batch <= 0 || y_div <= 0 ||
         batch > 65535)
         return SP_EINVAL;
-    const bool reads_v = op->kind == SP_OP_BLUR || op->kind == SP_OP_SR || op->kind == SP_OP_PSF ||
-                         op->kind == SP_OP_PHASE;
+    const bool reads_v = kind_of(op)->traits & SP_TRAIT_UPDATE_READS_V;
     if (!v && (reads_v || !y)) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = static_cast<int>(sp_rsq_partials(op));
     const int Pw = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(Pw, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
-    // BLUR, SR, PSF and PHASE read v: the identity-kind kernel over it (flat Philox element index)
+    // kinds that read v: the identity-kind kernel over it (flat Philox element index)
     const int opk = reads_v ? SP_OP_IDENTITY : op->kind;
 #define SP_K2(OPK, V, VIN, XIN)                                                            \
     launch_w(TK_DPS_UPDATE, (double)batch, k_dps_update<OPK, V, VIN, XIN>, grid, dim3(kBlock), s, *op, x, eps, y, \
@@ -720,8 +687,7 @@ int sp_predict_x0(const float* x, const float* eps, int64_t count, float a, floa
                   sp_stream_t stream) {
     if (!x || !eps || !out || count <= 0) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool v4 = count % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)eps % 16 == 0) &&
-                    ((uintptr_t)out % 16 == 0);
+    const bool v4 = count % 4 == 0 && aligned16(x) && aligned16(eps) && aligned16(out);
     if (v4)
         hipLaunchKernelGGL(k_predict_x0<4>, dim3(stride_blocks(count, 4, 1)), dim3(kBlock), 0, s,
                            x, eps, count, a, k, out);
@@ -762,86 +728,34 @@ int sp_residual_grad(const float* y, const float* z, int64_t batch, int64_t m, i
 
 int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_stream_t stream) {
     if (!valid_op(op) || !x || !y || batch <= 0 || batch > 65535) return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (op->kind) {
-        case SP_OP_IDENTITY: {
-            const hipError_t e = hipMemcpyAsync(y, x, sizeof(float) * op->n * batch,
-                                                hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) { set_error("sp_op_apply", e); return SP_ELAUNCH; }
-            return SP_OK;
-        }
-        case SP_OP_INPAINT: {
-            const dim3 grid(stride_blocks(op->n, op->n % 4 == 0 ? 4 : 1, batch), batch);
-            if (op->n % 4 == 0)
-                hipLaunchKernelGGL(k_inpaint_gather<4>, grid, dim3(kBlock), 0, s, *op, x, y);
-            else
-                hipLaunchKernelGGL(k_inpaint_gather<1>, grid, dim3(kBlock), 0, s, *op, x, y);
-            return check_launch("sp_op_apply");
-        }
-        case SP_OP_MASK: {
-            const dim3 grid(stride_blocks(op->n, op->n % 4 == 0 ? 4 : 1, batch), batch);
-            if (op->n % 4 == 0)
-                hipLaunchKernelGGL(k_mask<4>, grid, dim3(kBlock), 0, s, *op, x, y);
-            else
-                hipLaunchKernelGGL(k_mask<1>, grid, dim3(kBlock), 0, s, *op, x, y);
-            return check_launch("sp_op_apply");
-        }
-        case SP_OP_BLUR: return blur_apply(op, x, y, batch, s);
-        case SP_OP_SR: return sr_apply(op, x, y, batch, s);
-        case SP_OP_PSF: return psf_apply(op, x, y, batch, s);
-        case SP_OP_PHASE: return SP_EUNSUPPORTED;  // needs a workspace: sp_op_apply_ws
-    }
-    return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->apply) return SP_EUNSUPPORTED;  // needs a workspace: sp_op_apply_ws
+    return k->apply(op, x, y, batch, static_cast<hipStream_t>(stream));
 }
 
 int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
                    sp_stream_t stream) {
     if (!valid_op(op)) return SP_EINVAL;
-    if (op->kind != SP_OP_PHASE) return sp_op_apply(op, x, y, batch, stream);
+    const op_kind* k = kind_of(op);
+    if (!k->apply_ws) return sp_op_apply(op, x, y, batch, stream);
     if (!x || !y || !work || batch <= 0 || batch > 65535) return SP_EINVAL;
-    return phase_apply(op, x, y, batch, work, static_cast<hipStream_t>(stream));
+    return k->apply_ws(op, x, y, batch, work, static_cast<hipStream_t>(stream));
 }
 
 int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
                  float* work, sp_stream_t stream) {
     if (!valid_op(op)) return SP_EINVAL;
-    if (op->kind != SP_OP_PHASE) return SP_EUNSUPPORTED;  // linear kinds: sp_op_adjoint
+    const op_kind* k = kind_of(op);
+    if (!k->vjp_ws) return SP_EUNSUPPORTED;  // linear kinds: sp_op_adjoint
     if (!x || !g || !dx || !work || batch <= 0 || batch > 65535) return SP_EINVAL;
-    return phase_vjp(op, x, g, dx, batch, work, static_cast<hipStream_t>(stream));
+    return k->vjp_ws(op, x, g, dx, batch, work, static_cast<hipStream_t>(stream));
 }
 
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream) {
     if (!valid_op(op) || !x || !y || batch <= 0 || batch > 65535) return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (op->kind) {
-        case SP_OP_IDENTITY: {
-            const hipError_t e = hipMemcpyAsync(x, y, sizeof(float) * op->n * batch,
-                                                hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) { set_error("sp_op_adjoint", e); return SP_ELAUNCH; }
-            return SP_OK;
-        }
-        case SP_OP_INPAINT: {
-            const dim3 grid(stride_blocks(op->n, op->n % 4 == 0 ? 4 : 1, batch), batch);
-            if (op->n % 4 == 0)
-                hipLaunchKernelGGL(k_inpaint_scatter<4>, grid, dim3(kBlock), 0, s, *op, y, x);
-            else
-                hipLaunchKernelGGL(k_inpaint_scatter<1>, grid, dim3(kBlock), 0, s, *op, y, x);
-            return check_launch("sp_op_adjoint");
-        }
-        case SP_OP_MASK: {
-            const dim3 grid(stride_blocks(op->n, op->n % 4 == 0 ? 4 : 1, batch), batch);
-            if (op->n % 4 == 0)
-                hipLaunchKernelGGL(k_mask<4>, grid, dim3(kBlock), 0, s, *op, y, x);
-            else
-                hipLaunchKernelGGL(k_mask<1>, grid, dim3(kBlock), 0, s, *op, y, x);
-            return check_launch("sp_op_adjoint");
-        }
-        case SP_OP_BLUR: return blur_adjoint(op, y, x, batch, s);
-        case SP_OP_SR: return sr_adjoint(op, y, x, batch, s);
-        case SP_OP_PSF: return psf_adjoint(op, y, x, batch, s);
-        case SP_OP_PHASE: return SP_EUNSUPPORTED;  // nonlinear: sp_op_vjp_ws
-    }
-    return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->adjoint) return SP_EUNSUPPORTED;  // nonlinear: sp_op_vjp_ws
+    return k->adjoint(op, y, x, batch, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

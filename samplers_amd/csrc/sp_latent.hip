@@ -14,21 +14,9 @@
 #include <algorithm>
 
 #define SP_TU 3  // debug-build site numbering (sp_common.h SP_DCHECK)
-#include "sp_common.h"
+#include "sp_ops.h"
 
 namespace sp {
-
-int64_t tiles_elementwise(int64_t n);
-bool valid_op(const sp_op* op);
-
-// super-resolution entry points (sp_sr.hip)
-int sr_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
-                  float* x_eff, float* atr, float* partial, hipStream_t s);
-int sr_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* norm_sq,
-                      float omega, int64_t batch, float* out, hipStream_t s);
-int sr_pixel_opt(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq, const float* y,
-                 int64_t batch, int64_t y_div, float gs, const sp_adamw_coefs* c,
-                 const int32_t* stop, float* partial, hipStream_t s);
 
 // x_eff and A^T r for the elementwise operators (IDENTITY / INPAINT / MASK)
 template <int OPK, int V>
@@ -320,30 +308,9 @@ __global__ void k_opt_check_plateau(const float* __restrict__ p, int64_t count, 
     }
 }
 
-static inline unsigned grid_for(int64_t work, int V, int64_t batch) {
-    int64_t blocks = (work + (int64_t)kBlock * V - 1) / ((int64_t)kBlock * V);
-    const int64_t cap = std::max<int64_t>(1, 4096 / std::max<int64_t>(batch, 1));
-    return static_cast<unsigned>(std::max<int64_t>(1, std::min(blocks, cap)));
-}
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-}  // namespace sp
-
-using namespace sp;
-
-extern "C" {
-
-int sp_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
-                  float* x_eff, float* atr, float* rsq_partial, sp_stream_t stream) {
-    if (!valid_op(op) || !x0 || !y || !x_eff || !atr || !rsq_partial || batch <= 0 ||
-        batch > 65535 || y_div <= 0)
-        return SP_EINVAL;
-    if (op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF || op->kind == SP_OP_PHASE)
-        return SP_EUNSUPPORTED;  // kinds with a halo: composed from apply/adjoint by the caller
-                                 // (PHASE is nonlinear: no adjoint, no PSLD)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (op->kind == SP_OP_SR) return sr_psld_pixel(op, x0, y, batch, y_div, x_eff, atr, rsq_partial, s);
+// row functions of IDENTITY / INPAINT / MASK (sp_ops.h)
+int elementwise_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch,
+                           int64_t y_div, float* x_eff, float* atr, float* rsq_partial, hipStream_t s) {
     const int P = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(P, static_cast<unsigned>(batch));
     const bool v4 = op->n % 4 == 0;
@@ -358,37 +325,11 @@ int sp_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batc
     return check_launch("sp_psld_pixel");
 }
 
-int sp_sum_partials(const float* partials, int64_t count, float* out, sp_stream_t stream) {
-    if (!partials || !out || count <= 0) return SP_EINVAL;
-    launch(0, k_sum, dim3(1), dim3(kBlock), static_cast<hipStream_t>(stream), partials, count, out);
-    return check_launch("sp_sum_partials");
-}
-
-int sp_scaled_combine(const float* a, float alpha, const float* b, float beta, const float* norm_sq,
-                      int64_t count, float* out, sp_stream_t stream) {
-    if (!b || !out || count <= 0) return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool v4 = count % 4 == 0 && aligned16(b) && aligned16(out) && (!a || aligned16(a));
-    if (v4)
-        launch(0, k_scaled_combine<4>, dim3(grid_for(count, 4, 1)), dim3(kBlock), s, a, alpha, b,
-               beta, norm_sq, count, out);
-    else
-        launch(0, k_scaled_combine<1>, dim3(grid_for(count, 1, 1)), dim3(kBlock), s, a, alpha, b,
-               beta, norm_sq, count, out);
-    return check_launch("sp_scaled_combine");
-}
-
-int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* ata_u,
-                      const float* norm_sq, float omega, int64_t batch, float* out,
-                      sp_stream_t stream) {
-    if (!valid_op(op) || !atr || !u || !norm_sq || !out || batch <= 0 || batch > 65535)
-        return SP_EINVAL;
-    if (op->kind == SP_OP_PHASE) return SP_EUNSUPPORTED;  // nonlinear: no A^T A
-    if ((op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF) && !ata_u) return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (op->kind == SP_OP_SR) return sr_psld_cotangent(op, atr, u, norm_sq, omega, batch, out, s);
+int elementwise_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* ata_u,
+                               const float* norm_sq, float omega, int64_t batch, float* out,
+                               hipStream_t s) {
     const bool v4 = op->n % 4 == 0;
-    const dim3 grid(grid_for(op->n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
+    const dim3 grid(stride_blocks(op->n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
 #define SP_CT(OPK, V) \
     launch(0, k_psld_cotangent<OPK, V>, grid, dim3(kBlock), s, *op, atr, u, ata_u, norm_sq, omega, out)
     switch (op->kind) {
@@ -401,6 +342,71 @@ int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const f
     return check_launch("sp_psld_cotangent");
 }
 
+int elementwise_pixel_opt(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq, const float* y,
+                          int64_t batch, int64_t y_div, float grad_scale, const sp_adamw_coefs* c,
+                          const int32_t* stop, float* rsq_partial, hipStream_t s) {
+    const int P = static_cast<int>(tiles_elementwise(op->n));
+    const dim3 grid(P, static_cast<unsigned>(batch));
+    const bool v4 = op->n % 4 == 0;
+#define SP_PO(OPK, V)                                                                         \
+    launch(0, k_pixel_opt<OPK, V>, grid, dim3(kBlock), s, *op, x, exp_avg, exp_avg_sq, y, y_div, \
+           grad_scale, *c, stop, rsq_partial, P)
+    switch (op->kind) {
+        case SP_OP_IDENTITY: if (v4) SP_PO(SP_OP_IDENTITY, 4); else SP_PO(SP_OP_IDENTITY, 1); break;
+        case SP_OP_INPAINT: if (v4) SP_PO(SP_OP_INPAINT, 4); else SP_PO(SP_OP_INPAINT, 1); break;
+        default: if (v4) SP_PO(SP_OP_MASK, 4); else SP_PO(SP_OP_MASK, 1); break;
+    }
+#undef SP_PO
+    return check_launch("sp_pixel_opt_step");
+}
+
+}  // namespace sp
+
+using namespace sp;
+
+extern "C" {
+
+int sp_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
+                  float* x_eff, float* atr, float* rsq_partial, sp_stream_t stream) {
+    if (!valid_op(op) || !x0 || !y || !x_eff || !atr || !rsq_partial || batch <= 0 ||
+        batch > 65535 || y_div <= 0)
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->psld_pixel) return SP_EUNSUPPORTED;  // composed from apply / adjoint by the caller
+    return k->psld_pixel(op, x0, y, batch, y_div, x_eff, atr, rsq_partial, static_cast<hipStream_t>(stream));
+}
+
+int sp_sum_partials(const float* partials, int64_t count, float* out, sp_stream_t stream) {
+    if (!partials || !out || count <= 0) return SP_EINVAL;
+    launch(0, k_sum, dim3(1), dim3(kBlock), static_cast<hipStream_t>(stream), partials, count, out);
+    return check_launch("sp_sum_partials");
+}
+
+int sp_scaled_combine(const float* a, float alpha, const float* b, float beta, const float* norm_sq,
+                      int64_t count, float* out, sp_stream_t stream) {
+    if (!b || !out || count <= 0) return SP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool v4 = count % 4 == 0 && aligned16(b) && aligned16(out) && (!a || aligned16(a));
+    if (v4)
+        launch(0, k_scaled_combine<4>, dim3(stride_blocks(count, 4, 1)), dim3(kBlock), s, a, alpha, b,
+               beta, norm_sq, count, out);
+    else
+        launch(0, k_scaled_combine<1>, dim3(stride_blocks(count, 1, 1)), dim3(kBlock), s, a, alpha, b,
+               beta, norm_sq, count, out);
+    return check_launch("sp_scaled_combine");
+}
+
+int sp_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* ata_u,
+                      const float* norm_sq, float omega, int64_t batch, float* out,
+                      sp_stream_t stream) {
+    if (!valid_op(op) || !atr || !u || !norm_sq || !out || batch <= 0 || batch > 65535)
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->psld_cotangent) return SP_EUNSUPPORTED;  // nonlinear: no A^T A
+    if ((k->traits & SP_TRAIT_NEEDS_ATA_U) && !ata_u) return SP_EINVAL;
+    return k->psld_cotangent(op, atr, u, ata_u, norm_sq, omega, batch, out, static_cast<hipStream_t>(stream));
+}
+
 int sp_ddim_eps_step(const float* x, const float* eps, int64_t batch, int64_t n,
                      const sp_eps_coefs* c, const float* xi, uint64_t seed, int64_t step,
                      int64_t sample_offset, float* x_prev, float* x0, float* pseudo_x0,
@@ -408,7 +414,7 @@ int sp_ddim_eps_step(const float* x, const float* eps, int64_t batch, int64_t n,
     if (!x || !eps || !c || batch <= 0 || batch > 65535 || n <= 0) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool v4 = n % 4 == 0;
-    const dim3 grid(grid_for(n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
+    const dim3 grid(stride_blocks(n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
 #define SP_DE(V, XIN)                                                                       \
     launch(0, k_ddim_eps<V, XIN>, grid, dim3(kBlock), s, x, eps, n, *c, xi, seed, step,     \
            sample_offset, x_prev, x0, pseudo_x0)
@@ -424,7 +430,7 @@ int sp_stochastic_resample(const float* pseudo_x0, const float* x_t, int64_t bat
     if (!pseudo_x0 || !x_t || !out || batch <= 0 || batch > 65535 || n <= 0) return SP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool v4 = n % 4 == 0;
-    const dim3 grid(grid_for(n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
+    const dim3 grid(stride_blocks(n, v4 ? 4 : 1, batch), static_cast<unsigned>(batch));
 #define SP_SR(V, XIN)                                                                      \
     launch(0, k_stochastic_resample<V, XIN>, grid, dim3(kBlock), s, pseudo_x0, x_t, n, a_t, \
            sigma, xi, seed, step, sample_offset, out)
@@ -447,10 +453,10 @@ int sp_adamw_step_until(float* param, const float* grad, float* exp_avg, float* 
     const bool v4 = count % 4 == 0 && aligned16(param) && aligned16(grad) && aligned16(exp_avg) &&
                     aligned16(exp_avg_sq);
     if (v4)
-        launch(0, k_adamw<4>, dim3(grid_for(count, 4, 1)), dim3(kBlock), s, param, grad, exp_avg,
+        launch(0, k_adamw<4>, dim3(stride_blocks(count, 4, 1)), dim3(kBlock), s, param, grad, exp_avg,
                exp_avg_sq, count, *c, stop);
     else
-        launch(0, k_adamw<1>, dim3(grid_for(count, 1, 1)), dim3(kBlock), s, param, grad, exp_avg,
+        launch(0, k_adamw<1>, dim3(stride_blocks(count, 1, 1)), dim3(kBlock), s, param, grad, exp_avg,
                exp_avg_sq, count, *c, stop);
     return check_launch("sp_adamw_step");
 }
@@ -462,25 +468,10 @@ int sp_pixel_opt_step(const sp_op* op, float* x, float* exp_avg, float* exp_avg_
     if (!valid_op(op) || !x || !exp_avg || !exp_avg_sq || !y || !c || !rsq_partial ||
         batch <= 0 || batch > 65535 || y_div <= 0)
         return SP_EINVAL;
-    if (op->kind == SP_OP_BLUR || op->kind == SP_OP_PSF || op->kind == SP_OP_PHASE)
-        return SP_EUNSUPPORTED;  // composed by the caller (PHASE: nonlinear, no adjoint)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (op->kind == SP_OP_SR)
-        return sr_pixel_opt(op, x, exp_avg, exp_avg_sq, y, batch, y_div, grad_scale, c, stop,
-                            rsq_partial, s);
-    const int P = static_cast<int>(tiles_elementwise(op->n));
-    const dim3 grid(P, static_cast<unsigned>(batch));
-    const bool v4 = op->n % 4 == 0;
-#define SP_PO(OPK, V)                                                                         \
-    launch(0, k_pixel_opt<OPK, V>, grid, dim3(kBlock), s, *op, x, exp_avg, exp_avg_sq, y, y_div, \
-           grad_scale, *c, stop, rsq_partial, P)
-    switch (op->kind) {
-        case SP_OP_IDENTITY: if (v4) SP_PO(SP_OP_IDENTITY, 4); else SP_PO(SP_OP_IDENTITY, 1); break;
-        case SP_OP_INPAINT: if (v4) SP_PO(SP_OP_INPAINT, 4); else SP_PO(SP_OP_INPAINT, 1); break;
-        default: if (v4) SP_PO(SP_OP_MASK, 4); else SP_PO(SP_OP_MASK, 1); break;
-    }
-#undef SP_PO
-    return check_launch("sp_pixel_opt_step");
+    const op_kind* k = kind_of(op);
+    if (!k->pixel_opt) return SP_EUNSUPPORTED;  // composed by the caller
+    return k->pixel_opt(op, x, exp_avg, exp_avg_sq, y, batch, y_div, grad_scale, c, stop, rsq_partial,
+                        static_cast<hipStream_t>(stream));
 }
 
 int sp_opt_check(const float* partials, int64_t count, float total, double threshold,

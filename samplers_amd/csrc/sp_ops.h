@@ -1,0 +1,73 @@
+// Per-kind dispatch of the operator entry points (internal; includes sp_common.h).  Every
+// `extern "C"` entry that takes an sp_op checks its common arguments, looks the kind's row up and
+// calls through it.  The rows are filled in sp_dps.hip; a kind's functions live in its own file
+// (IDENTITY / INPAINT / MASK share one set, next to their kernels in sp_dps.hip and sp_latent.hip)
+// and are called with a descriptor that passed valid_op() and the entry's arguments checked.
+#pragma once
+
+#include "sp_common.h"
+
+namespace sp {
+
+struct dps_residual_args {
+    const float *x, *eps, *y;
+    int64_t batch, y_div;
+    float a, k, gs;
+    const sp_step_rec* sched;  // with cursor: the device-resident schedule, else both null
+    const int32_t* cursor;
+    float *v, *partial;
+    float* work;  // null in the forms without a workspace and where the kind needs none
+};
+
+typedef bool valid_fn(const sp_op* op);
+typedef int64_t partials_fn(const sp_op* op);
+typedef int64_t workspace_fn(const sp_op* op, int64_t batch);
+typedef int dps_residual_fn(const sp_op* op, const dps_residual_args& r, hipStream_t s);
+typedef int map_fn(const sp_op* op, const float* in, float* out, int64_t batch, hipStream_t s);
+typedef int apply_ws_fn(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                        hipStream_t s);
+typedef int vjp_ws_fn(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
+                      float* work, hipStream_t s);
+typedef int psld_pixel_fn(const sp_op* op, const float* x0, const float* y, int64_t batch,
+                          int64_t y_div, float* x_eff, float* atr, float* partial, hipStream_t s);
+typedef int psld_cotangent_fn(const sp_op* op, const float* atr, const float* u, const float* ata_u,
+                              const float* norm_sq, float omega, int64_t batch, float* out,
+                              hipStream_t s);
+typedef int pixel_opt_fn(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq,
+                         const float* y, int64_t batch, int64_t y_div, float gs,
+                         const sp_adamw_coefs* c, const int32_t* stop, float* partial, hipStream_t s);
+
+// One row per sp_op kind.  A null member is the library's answer for a kind without that pass:
+// 0 floats of workspace, or SP_EUNSUPPORTED (apply_ws: sp_op_apply).
+struct op_kind {
+    valid_fn* valid;        // the kind's geometry rules
+    partials_fn* partials;  // r^2 partials per sample
+    workspace_fn *dps_workspace, *op_workspace;
+    dps_residual_fn* dps_residual;
+    map_fn *apply, *adjoint;  // the linear kinds
+    apply_ws_fn* apply_ws;    // the nonlinear kinds (with vjp_ws)
+    vjp_ws_fn* vjp_ws;
+    psld_pixel_fn* psld_pixel;
+    psld_cotangent_fn* psld_cotangent;
+    pixel_opt_fn* pixel_opt;
+    uint32_t traits;  // SP_TRAIT_* (samplers_hip.h)
+};
+
+const op_kind* kind_of(const sp_op* op);  // null for an unknown kind or a null op
+bool valid_op(const sp_op* op);
+int64_t tiles_elementwise(int64_t n);
+
+// the kinds' functions, one line per column of the table (sp_blur.hip, sp_sr.hip, sp_psf.hip,
+// sp_phase.hip; elementwise_*: sp_latent.hip, the cotangent serves BLUR and PSF over A^T A u too)
+valid_fn blur_valid, sr_valid, psf_valid, phase_valid;
+partials_fn blur_partials, sr_partials, psf_partials, phase_partials;
+workspace_fn psf_workspace, phase_workspace;
+dps_residual_fn blur_dps_residual, sr_dps_residual, psf_dps_residual, phase_dps_residual;
+map_fn blur_apply, blur_adjoint, sr_apply, sr_adjoint, psf_apply, psf_adjoint;
+apply_ws_fn phase_apply;
+vjp_ws_fn phase_vjp;
+psld_pixel_fn elementwise_psld_pixel, sr_psld_pixel;
+psld_cotangent_fn elementwise_psld_cotangent, sr_psld_cotangent;
+pixel_opt_fn elementwise_pixel_opt, sr_pixel_opt;
+
+}  // namespace sp

@@ -49,7 +49,7 @@
 #include <algorithm>
 
 #define SP_TU 17  // debug-build site numbering (sp_common.h SP_DCHECK)
-#include "sp_common.h"
+#include "sp_ops.h"
 
 namespace sp {
 
@@ -73,7 +73,8 @@ static inline int phase_lines(int N) {
 
 static inline int phase_lds_bytes(int N) { return 8 * N + 16 * phase_lines(N) * phase_np(N); }
 
-bool phase_size_ok(int N) {
+// 2^k or 3 * 2^k in [8, 1024]
+static bool phase_size_ok(int N) {
     if (N < 8 || N > 1024) return false;
     while (N % 2 == 0) N /= 2;
     return N == 1 || N == 3;
@@ -359,6 +360,15 @@ __global__ __launch_bounds__(kBlock) void k_phase_rows_inv(sp_op op, const float
 // ---------------------------------------------------------------------------
 // host side (called from the entry points in sp_dps.hip; `op` is valid)
 // ---------------------------------------------------------------------------
+bool phase_valid(const sp_op* op) {  // radius = pad_h, factor = pad_w
+    return !op->taps && !op->keep_bits && !op->word_rank && op->radius >= 0 && op->factor >= 0 &&
+           op->channels > 0 && op->height > 0 && op->width > 0 && op->height <= 1024 &&
+           op->width <= 1024 && op->radius <= 512 && op->factor <= 512 &&
+           phase_size_ok(op->height + 2 * op->radius) && phase_size_ok(op->width + 2 * op->factor) &&
+           (int64_t)op->channels * op->height * op->width == op->n &&
+           (int64_t)op->channels * (op->height + 2 * op->radius) * (op->width + 2 * op->factor) == op->m;
+}
+
 static inline int phase_col_tiles(const sp_op* op) {
     const phase_geom g(*op);
     const int T = phase_lines(g.Nh);
@@ -379,67 +389,56 @@ int64_t phase_workspace(const sp_op* op, int64_t batch) {
     return 2 * batch * g.C * (int64_t)g.Nw * g.H;
 }
 
-template <typename K, typename... Args>
-static inline void phase_launch(int kind, double work, K kernel, unsigned gx, int64_t batch, int N,
-                                hipStream_t s, Args... args) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (kind && timing_on()) timing_events(kind, work, &e0, &e1);
-    hipExtLaunchKernelGGL(kernel, dim3(gx, static_cast<unsigned>(batch)), dim3(kBlock),
-                          phase_lds_bytes(N), s, e0, e1, 0, args...);
+// rows (x -> ws), then the column pass of MODE: PH_APPLY (-> y) or PH_VJP (gy -> ws)
+template <int MODE>
+static int phase_forward(const char* what, const sp_op* op, const float* x, const float* gy, float* y,
+                         int64_t batch, float2* ws, hipStream_t s) {
+    const phase_geom g(*op);
+    launch_w(0, 0.0, k_phase_rows<false>, sample_grid(op->channels * phase_row_tiles(op), batch),
+             dim3(kBlock), phase_lds_bytes(g.Nw), s, *op, x, (const float*)nullptr, 1.f, 0.f, ws,
+             phase_lines(g.Nw), (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
+    const int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(0, 0.0, k_phase_cols<MODE>, sample_grid(op->channels * phase_col_tiles(op), batch),
+             dim3(kBlock), phase_lds_bytes(g.Nh), s, *op, ws, gy, (int64_t)1, 0.f, y, (float*)nullptr, 0,
+             phase_lines(g.Nh), (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
+    return check_launch(what);
 }
 
 int phase_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
                 hipStream_t s) {
-    const phase_geom g(*op);
-    float2* ws = reinterpret_cast<float2*>(work);
-    phase_launch(0, 0.0, k_phase_rows<false>, op->channels * phase_row_tiles(op), batch, g.Nw, s, *op,
-                 x, (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), (const sp_step_rec*)nullptr,
-                 (const int32_t*)nullptr);
-    int rc = check_launch("sp_op_apply_ws");
-    if (rc != SP_OK) return rc;
-    phase_launch(0, 0.0, k_phase_cols<PH_APPLY>, op->channels * phase_col_tiles(op), batch, g.Nh, s,
-                 *op, ws, (const float*)nullptr, (int64_t)1, 0.f, y, (float*)nullptr, 0, phase_lines(g.Nh),
-                 (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    return check_launch("sp_op_apply_ws");
+    return phase_forward<PH_APPLY>("sp_op_apply_ws", op, x, nullptr, y, batch,
+                                   reinterpret_cast<float2*>(work), s);
 }
 
 int phase_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
               float* work, hipStream_t s) {
-    const phase_geom g(*op);
     float2* ws = reinterpret_cast<float2*>(work);
-    phase_launch(0, 0.0, k_phase_rows<false>, op->channels * phase_row_tiles(op), batch, g.Nw, s, *op,
-                 x, (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), (const sp_step_rec*)nullptr,
-                 (const int32_t*)nullptr);
-    int rc = check_launch("sp_op_vjp_ws");
+    const int rc = phase_forward<PH_VJP>("sp_op_vjp_ws", op, x, gy, nullptr, batch, ws, s);
     if (rc != SP_OK) return rc;
-    phase_launch(0, 0.0, k_phase_cols<PH_VJP>, op->channels * phase_col_tiles(op), batch, g.Nh, s, *op,
-                 ws, gy, (int64_t)1, 0.f, (float*)nullptr, (float*)nullptr, 0, phase_lines(g.Nh),
-                 (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    rc = check_launch("sp_op_vjp_ws");
-    if (rc != SP_OK) return rc;
-    phase_launch(0, 0.0, k_phase_rows_inv, op->channels * phase_row_tiles(op), batch, g.Nw, s, *op,
-                 (const float2*)ws, dx, phase_lines(g.Nw));
+    const int Nw = phase_geom(*op).Nw;
+    launch_w(0, 0.0, k_phase_rows_inv, sample_grid(op->channels * phase_row_tiles(op), batch),
+             dim3(kBlock), phase_lds_bytes(Nw), s, *op, (const float2*)ws, dx, phase_lines(Nw));
     return check_launch("sp_op_vjp_ws");
 }
 
 // rows (x, eps -> work), columns (work, y -> work, partials), rows^-1 (work -> v)
-int phase_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                       int64_t batch, int64_t y_div, float a, float k, float gs,
-                       const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
-                       float* partial, hipStream_t s) {
+int phase_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
     const phase_geom g(*op);
-    float2* ws = reinterpret_cast<float2*>(work);
+    float2* ws = reinterpret_cast<float2*>(r.work);
     const int P = static_cast<int>(phase_partials(op));
-    phase_launch(TK_DPS_RESIDUAL, (double)batch, k_phase_rows<true>, op->channels * phase_row_tiles(op),
-                 batch, g.Nw, s, *op, x, eps, a, k, ws, phase_lines(g.Nw), sched, cursor);
+    const dim3 rows = sample_grid(op->channels * phase_row_tiles(op), r.batch);
+    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_phase_rows<true>, rows, dim3(kBlock),
+             phase_lds_bytes(g.Nw), s, *op, r.x, r.eps, r.a, r.k, ws, phase_lines(g.Nw), r.sched, r.cursor);
     int rc = check_launch("sp_dps_residual_ws");
     if (rc != SP_OK) return rc;
-    phase_launch(TK_DPS_RESIDUAL, 0.0, k_phase_cols<PH_RESIDUAL>, static_cast<unsigned>(P), batch, g.Nh,
-                 s, *op, ws, y, y_div, gs, (float*)nullptr, partial, P, phase_lines(g.Nh), sched, cursor);
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_phase_cols<PH_RESIDUAL>, sample_grid(P, r.batch), dim3(kBlock),
+             phase_lds_bytes(g.Nh), s, *op, ws, r.y, r.y_div, r.gs, (float*)nullptr, r.partial, P,
+             phase_lines(g.Nh), r.sched, r.cursor);
     rc = check_launch("sp_dps_residual_ws");
     if (rc != SP_OK) return rc;
-    phase_launch(TK_DPS_RESIDUAL, 0.0, k_phase_rows_inv, op->channels * phase_row_tiles(op), batch, g.Nw,
-                 s, *op, (const float2*)ws, v, phase_lines(g.Nw));
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_phase_rows_inv, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, *op,
+             (const float2*)ws, r.v, phase_lines(g.Nw));
     return check_launch("sp_dps_residual_ws");
 }
 

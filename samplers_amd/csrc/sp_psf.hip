@@ -40,11 +40,9 @@
 #include <algorithm>
 
 #define SP_TU 16  // debug-build site numbering (sp_common.h SP_DCHECK)
-#include "sp_common.h"
+#include "sp_ops.h"
 
 namespace sp {
-
-bool valid_op(const sp_op* op);
 
 constexpr int PTH = 32, PTW = 64;  // output tile
 constexpr int PNX = 8;             // adjacent outputs per thread
@@ -318,51 +316,50 @@ __global__ __launch_bounds__(kBlock) void k_psf(sp_op op, const float* __restric
 // ---------------------------------------------------------------------------
 // host side (called from the entry points in sp_dps.hip; `op` is valid)
 // ---------------------------------------------------------------------------
+bool psf_valid(const sp_op* op) {
+    return op->taps && op->radius >= 1 && op->radius <= 30 && op->m == op->n && op->channels > 0 &&
+           (int64_t)op->channels * op->height * op->width == op->n &&
+           op->height > 2 * op->radius && op->width > 2 * op->radius;
+}
+
 // tiles per sample = workgroups per sample = r^2 partials per sample
 int64_t psf_partials(const sp_op* op) {
     return (int64_t)op->channels * ((op->height + PTH - 1) / PTH) * ((op->width + PTW - 1) / PTW);
 }
 
-template <typename K, typename... Args>
-static inline void psf_launch(int kind, double work, K kernel, const sp_op* op, int64_t batch,
-                              hipStream_t s, Args... args) {
-    const psf_geom g(op->radius);
-    const dim3 grid(static_cast<unsigned>(psf_partials(op)), static_cast<unsigned>(batch));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (kind && timing_on()) timing_events(kind, work, &e0, &e1);
-    hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), sizeof(float) * g.floats(), s, e0, e1, 0, args...);
+// floats of grad_scale * r between the residual and the adjoint launch
+int64_t psf_workspace(const sp_op* op, int64_t batch) { return batch * op->m; }
+
+static inline size_t psf_lds_bytes(const sp_op* op) { return sizeof(float) * psf_geom(op->radius).floats(); }
+
+// out = A in (PSF_APPLY) or A^T in (PSF_ADJOINT): the kernel's plain map, no x0, no residual
+template <int MODE>
+static int psf_map(int kind, const char* what, const sp_op* op, const float* in, float* out,
+                   int64_t batch, hipStream_t s) {
+    const int64_t P = psf_partials(op);
+    launch_w(kind, 0.0, k_psf<MODE>, sample_grid(P, batch), dim3(kBlock), psf_lds_bytes(op), s, *op, in,
+             (const float*)nullptr, (const float*)nullptr, (int64_t)1, 1.f, 0.f, 0.f, out,
+             (float*)nullptr, static_cast<int>(P), (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
+    return check_launch(what);
 }
 
 int psf_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s) {
-    const int P = static_cast<int>(psf_partials(op));
-    psf_launch(0, 0.0, k_psf<PSF_APPLY>, op, batch, s, *op, x, (const float*)nullptr,
-               (const float*)nullptr, (int64_t)1, 1.f, 0.f, 0.f, y, (float*)nullptr, P,
-               (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    return check_launch("sp_op_apply");
+    return psf_map<PSF_APPLY>(0, "sp_op_apply", op, x, y, batch, s);
 }
 
 int psf_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStream_t s) {
-    const int P = static_cast<int>(psf_partials(op));
-    psf_launch(0, 0.0, k_psf<PSF_ADJOINT>, op, batch, s, *op, y, (const float*)nullptr,
-               (const float*)nullptr, (int64_t)1, 1.f, 0.f, 0.f, x, (float*)nullptr, P,
-               (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    return check_launch("sp_op_adjoint");
+    return psf_map<PSF_ADJOINT>(0, "sp_op_adjoint", op, y, x, batch, s);
 }
 
 // residual (x, eps, y -> work = grad_scale r, partials), then adjoint (work -> v)
-int psf_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                     int64_t batch, int64_t y_div, float a, float k, float gs,
-                     const sp_step_rec* sched, const int32_t* cursor, float* v, float* work,
-                     float* partial, hipStream_t s) {
-    const int P = static_cast<int>(psf_partials(op));
-    psf_launch(TK_DPS_RESIDUAL, (double)batch, k_psf<PSF_RESIDUAL>, op, batch, s, *op, x, eps, y,
-               y_div, a, k, gs, work, partial, P, sched, cursor);
+int psf_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    const int64_t P = psf_partials(op);
+    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_psf<PSF_RESIDUAL>, sample_grid(P, r.batch), dim3(kBlock),
+             psf_lds_bytes(op), s, *op, r.x, r.eps, r.y, r.y_div, r.a, r.k, r.gs, r.work, r.partial,
+             static_cast<int>(P), r.sched, r.cursor);
     const int rc = check_launch("sp_dps_residual_ws");
     if (rc != SP_OK) return rc;
-    psf_launch(TK_DPS_RESIDUAL, 0.0, k_psf<PSF_ADJOINT>, op, batch, s, *op, (const float*)work,
-               (const float*)nullptr, (const float*)nullptr, (int64_t)1, 1.f, 0.f, 0.f, v,
-               (float*)nullptr, P, (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    return check_launch("sp_dps_residual_ws");
+    return psf_map<PSF_ADJOINT>(TK_DPS_RESIDUAL, "sp_dps_residual_ws", op, r.work, r.v, r.batch, s);
 }
 
 }  // namespace sp

@@ -24,11 +24,9 @@
 #include <algorithm>
 
 #define SP_TU 15  // debug-build site numbering (sp_common.h SP_DCHECK)
-#include "sp_common.h"
+#include "sp_ops.h"
 
 namespace sp {
-
-bool valid_op(const sp_op* op);
 
 template <int S, int PW>
 struct sr_cfg {
@@ -378,6 +376,14 @@ static inline int64_t sr_tile(const sp_op* op) {
                                                                    : sr_cfg<8, 4>::kTile;
 }
 
+bool sr_valid(const sp_op* op) {
+    return (op->factor == 2 || op->factor == 4 || op->factor == 8) && op->channels > 0 &&
+           op->height > 0 && op->width > 0 &&
+           (int64_t)op->channels * op->height * op->width == op->n &&
+           op->height % op->factor == 0 && op->width % op->factor == 0 &&
+           op->m * op->factor * op->factor == op->n;
+}
+
 // tiles per sample = r^2 partials per sample
 int64_t sr_partials(const sp_op* op) {
     const int64_t patches = op->n / ((int64_t)op->factor * (sr_vec(op) ? 4 : 2));
@@ -409,13 +415,11 @@ int sr_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, hipStre
     return check_launch("sp_op_adjoint");
 }
 
-int sr_dps_residual(const sp_op* op, const float* x, const float* eps, const float* y,
-                    int64_t batch, int64_t y_div, float a, float k, float gs,
-                    const sp_step_rec* sched, const int32_t* cursor, float* v, float* partial,
-                    hipStream_t s) {
+int sr_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
     const int P = static_cast<int>(sr_partials(op));
-    SR_LAUNCH(TK_DPS_RESIDUAL, (double)batch, k_sr_dps_residual, *op, x, eps, y, y_div, a, k, gs, v,
-              partial, P, sched, cursor);
+    const int64_t batch = r.batch;
+    SR_LAUNCH(TK_DPS_RESIDUAL, (double)batch, k_sr_dps_residual, *op, r.x, r.eps, r.y, r.y_div, r.a, r.k,
+              r.gs, r.v, r.partial, P, r.sched, r.cursor);
     return check_launch("sp_dps_residual");
 }
 
@@ -426,7 +430,8 @@ int sr_psld_pixel(const sp_op* op, const float* x0, const float* y, int64_t batc
     return check_launch("sp_psld_pixel");
 }
 
-int sr_psld_cotangent(const sp_op* op, const float* atr, const float* u, const float* norm_sq,
+int sr_psld_cotangent(const sp_op* op, const float* atr, const float* u,
+                      const float* /*ata_u: A^T A u is computed in the kernel*/, const float* norm_sq,
                       float omega, int64_t batch, float* out, hipStream_t s) {
     SR_LAUNCH(0, 0.0, k_sr_psld_cotangent, *op, atr, u, norm_sq, omega, out);
     return check_launch("sp_psld_cotangent");

@@ -149,7 +149,8 @@ class FusedDPSStep:
             raise _hip.HipLibraryError(f"operator descriptor rejected ({self.partials})")
         if mode not in ("dps", "pgdm"):
             raise ValueError(mode)
-        if mode == "pgdm" and desc.kind == _hip.SP_OP_PHASE:
+        self.traits = int(self.lib.sp_op_traits(desc))
+        if mode == "pgdm" and not self.traits & _hip.SP_TRAIT_LINEAR:
             raise NotImplementedError(f"{type(op).__name__} is nonlinear and has no "
                                       "apply_pseudo_inverse: PGDM does not apply")
         self.mode = mode
@@ -172,12 +173,9 @@ class FusedDPSStep:
         self.gamma, self.eta = float(gamma), float(eta)
         # pass 2 re-derives v from (x, eps, y) (default: SURVEY §8d's minimal bytes, 4n + m per
         # sample; with non-temporal loads and 2 float4 groups per thread it is 7 % faster than
-        # re-reading pass 1's v, 42.3 vs 45.2 us at B = 64, 256^2) or re-reads v (reuse_v).
-        # Blur always re-reads it (its adjoint needs a halo), and so does super-resolution (v is
-        # constant over a block; pass 2 stays the flat identity-kind kernel), the PSF blur and phase
-        # retrieval (v = J^T(grad_scale r) comes out of its FFT passes).
-        self.needs_v = desc.kind in (_hip.SP_OP_BLUR, _hip.SP_OP_SR, _hip.SP_OP_PSF,
-                                     _hip.SP_OP_PHASE) or bool(reuse_v)
+        # re-reading pass 1's v, 42.3 vs 45.2 us at B = 64, 256^2) or re-reads v (reuse_v, and
+        # always for the kinds whose pass 2 is the identity-kind kernel over v: the library's trait).
+        self.needs_v = bool(self.traits & _hip.SP_TRAIT_UPDATE_READS_V) or bool(reuse_v)
         self.micro_batch = micro_batch
         self.timer = timer
 
@@ -194,7 +192,7 @@ class FusedDPSStep:
         """Pass 1's work buffer for ``batch`` samples (``sp_dps_workspace`` floats; None where
         the operator's pass needs none).  Allocated by torch on the launch stream, so a graph
         capture records it like every other buffer of the step."""
-        if self.desc.kind not in (_hip.SP_OP_PSF, _hip.SP_OP_PHASE):  # one-pass kinds: no host call in the step loop
+        if not self.traits & _hip.SP_TRAIT_DPS_WORKSPACE:  # one-pass kinds: no host call in the step loop
             return None
         floats = int(self.lib.sp_dps_workspace(self.desc, batch))
         if floats < 0:

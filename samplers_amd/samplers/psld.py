@@ -80,8 +80,8 @@ class FusedPSLDStep:
         self.y_div = int(y_div)
         # operators without a HIP descriptor: A, A^T and their VJPs by torch autograd
         self.generic = desc is None
-        # kinds with a halo (Gaussian and PSF blur): the pixel pass composed from A and A^T
-        self.blur = not self.generic and desc.kind in _hip.HALO_KINDS
+        # kinds without a fused pixel pass (Gaussian and PSF blur): composed from A and A^T
+        self.blur = not self.generic and not self.lib.sp_op_traits(desc) & _hip.SP_TRAIT_FUSED_LATENT
         if self.generic:
             self.n, self.m = int(math.prod(op.x_shape)), int(math.prod(op.y_shape))
         else:

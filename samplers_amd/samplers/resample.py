@@ -280,7 +280,7 @@ class ReSampleSampler(PosteriorSampler, Generic[Condition_co]):
         gs = float(np.float32(-2.0 / total))  # mse_loss backward w.r.t. A x: 2 (Ax - y) / M
         tot, thr = float(np.float32(total)), float(eps) ** 2
         generic = cons.desc is None
-        fused = not generic and int(cons.desc.kind) not in _hip.HALO_KINDS
+        fused = not generic and bool(lib.sp_op_traits(cons.desc) & _hip.SP_TRAIT_FUSED_LATENT)
         shared = dist.is_initialized() and dist.get_world_size(cons.group) > 1
         part = torch.empty(b, int(lib.sp_rsq_partials(cons.desc)), device=x.device) if fused else None
         ss = torch.empty(1, device=x.device)
