@@ -592,7 +592,9 @@ int sp_gemm_x6_layout_ws(const float* x, const float* wp, const float* bias, con
  * replaces the scores / softmax / weighted-sum chain and its autograd VJP) on fp32 MFMA,
  * without materialising the score matrix.  q, k, v, out, dout, dq, dk, dv: [bh][n][d];
  * lse, delta: [bh][n] (lse = row log-sum-exp, natural log, written by the forward; delta =
- * rowsum(dout * out), written by the backward).  Self-attention only (m == n); head dims 40,
+ * rowsum(dout * out), written by the backward; at the split-bf16 forward's shapes the dq pass
+ * replaces it by sum_j P dP / sum_j P of the P it rebuilds, which the dk / dv pass then reads).
+ * Self-attention only (m == n); head dims 40,
  * 80, 160; n a multiple of the kernels' row blocks (see _supported).  The backward writes dq
  * when dq != NULL and dk, dv when both are given. */
 int sp_attention_supported(int64_t bh, int64_t n, int64_t m, int32_t d);

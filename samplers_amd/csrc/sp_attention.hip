@@ -274,13 +274,20 @@ __global__ __launch_bounds__(kBlock) void k_attn_delta(const float* __restrict__
 
 // ---- backward: dq ---------------------------------------------------------------------------
 // As the forward, with dP^T = V dO^T beside S^T and dQ^T += K^T dS^T, dS = P (dP - delta).
-template <int D>
+// CORR: the forward may have been the split-bf16 kernel (sp_attention6.hip), whose scores round
+// differently from the ones P is rebuilt from here.  delta = rowsum(dO o O) then differs from
+// sum_j P_ij dP_ij / sum_j P_ij by rho_i, the rows of dS sum to rho_i sum_j P_ij instead of 0, and
+// dq is off by scale rho_i sum_j P_ij k_j — the rounding difference (1e-6) times the weighted
+// mean key, which peaked rows make large.  So the kernel also accumulates sum_j dS_ij,
+// sum_j P_ij and K^T P^T, stores dq = scale (K^T dS^T - rho K^T P^T) and writes delta + rho
+// back for k_attn_dkv (each query's delta is read by its own workgroup only).
+template <int D, bool CORR = false>
 __global__ __launch_bounds__(kBlock) void k_attn_dq(const float* __restrict__ q,
                                                     const float* __restrict__ k,
                                                     const float* __restrict__ v,
                                                     const float* __restrict__ dout,
                                                     const float* __restrict__ lse,
-                                                    const float* __restrict__ delta, int n,
+                                                    float* __restrict__ delta, int n,
                                                     int heads, int rs, int ro, AtKV kv, float sl2,
                                                     float scale, float* __restrict__ dq) {
     using G = AtGeo<D>;
@@ -314,6 +321,16 @@ __global__ __launch_bounds__(kBlock) void k_attn_dq(const float* __restrict__ q,
     for (int t = 0; t < G::QT; ++t)
 #pragma unroll
         for (int dt = 0; dt < G::DT; ++dt) acc[t][dt] = at_f4{0.f, 0.f, 0.f, 0.f};
+    at_f4 accp[CORR ? G::QT : 1][CORR ? G::DT : 1];  // K^T P^T
+    float rsum[G::QT], psum[G::QT];                 // this lane's part of sum_j dS_ij, sum_j P_ij
+    if constexpr (CORR) {
+#pragma unroll
+        for (int t = 0; t < G::QT; ++t) {
+            rsum[t] = psum[t] = 0.f;
+#pragma unroll
+            for (int dt = 0; dt < G::DT; ++dt) accp[t][dt] = at_f4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
 
     AtStage<D> sk, sv;
     const int rk = kv.rs;
@@ -354,11 +371,15 @@ __global__ __launch_bounds__(kBlock) void k_attn_dq(const float* __restrict__ q,
 #pragma unroll
                         for (int t = 0; t < G::QT; ++t) s[t][i] = -INFINITY;
             }
-            float ds[G::QT][4];
+            float ds[G::QT][4], p[G::QT][4];
 #pragma unroll
             for (int t = 0; t < G::QT; ++t)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) ds[t][i] = at_exp2(s[t][i] - ls[t]) * (dp[t][i] - de[t]);
+                for (int i = 0; i < 4; ++i) {
+                    p[t][i] = at_exp2(s[t][i] - ls[t]);
+                    ds[t][i] = p[t][i] * (dp[t][i] - de[t]);
+                    if constexpr (CORR) rsum[t] += ds[t][i], psum[t] += p[t][i];
+                }
             // dQ^T += K^T dS^T: k-step i takes key 4 kl + i (A: K[key][dt*16 + li])
             const float* kt = Ks + (sb * 16 + 4 * kl) * G::DP + li;
 #pragma unroll
@@ -367,8 +388,26 @@ __global__ __launch_bounds__(kBlock) void k_attn_dq(const float* __restrict__ q,
                 for (int dt = 0; dt < G::DT; ++dt) {
                     const float a = kt[i * G::DP + 16 * dt];
 #pragma unroll
-                    for (int t = 0; t < G::QT; ++t) acc[t][dt] = at_mfma(a, ds[t][i], acc[t][dt]);
+                    for (int t = 0; t < G::QT; ++t) {
+                        acc[t][dt] = at_mfma(a, ds[t][i], acc[t][dt]);
+                        if constexpr (CORR) accp[t][dt] = at_mfma(a, p[t][i], accp[t][dt]);
+                    }
                 }
+        }
+    }
+    if constexpr (CORR) {
+#pragma unroll
+        for (int t = 0; t < G::QT; ++t) {
+            // query li's sums over its four key groups (lanes li + 16 kl); its largest weight is ~1
+            float r = rsum[t], l = psum[t];
+            r += __shfl_xor(r, 16), l += __shfl_xor(l, 16);
+            r += __shfl_xor(r, 32), l += __shfl_xor(l, 32);
+            const float rho = r / l;
+#pragma unroll
+            for (int dt = 0; dt < G::DT; ++dt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[t][dt][j] = fmaf(-rho, accp[t][dt][j], acc[t][dt][j]);
+            if (kl == 0) delta[(int64_t)blockIdx.y * n + q0 + 16 * t + li] = de[t] + rho;
         }
     }
 #pragma unroll
@@ -517,15 +556,22 @@ static int attn_fwd_d(const float* q, const float* k, const float* v, int64_t bh
 template <int D>
 static int attn_bwd_d(const float* q, const float* k, const float* v, const float* out,
                       const float* dout, const float* lse, int64_t bh, int heads, int64_t n, int rs, int ro,
-                      AtKV kv, float scale, float* delta, float* dq, float* dk, float* dv, hipStream_t s) {
+                      AtKV kv, float scale, float* delta, float* dq, float* dk, float* dv, hipStream_t s,
+                      bool corr = false) {
     using G = AtGeo<D>;
     const int64_t rows = bh * n;
     launch(0, k_attn_delta<D>, dim3(static_cast<unsigned>((rows + kBlock - 1) / kBlock)), dim3(kBlock), s,
            out, dout, rows, static_cast<int>(n), heads, ro, delta);
     const dim3 grid(static_cast<unsigned>(n / G::WB), static_cast<unsigned>(bh));
     const float sl2 = scale * AT_LOG2E;
-    if (dq) launch(0, k_attn_dq<D>, grid, dim3(kBlock), s, q, k, v, dout, lse, (const float*)delta,
-                   static_cast<int>(n), heads, rs, ro, kv, sl2, scale, dq);
+    if constexpr (D <= 80) {  // the split-bf16 forward's head dims
+        if (dq && corr)
+            launch(0, k_attn_dq<D, true>, grid, dim3(kBlock), s, q, k, v, dout, lse, delta, static_cast<int>(n),
+                   heads, rs, ro, kv, sl2, scale, dq);
+    }
+    if (dq && !(corr && D <= 80))
+        launch(0, k_attn_dq<D>, grid, dim3(kBlock), s, q, k, v, dout, lse, delta, static_cast<int>(n), heads, rs,
+               ro, kv, sl2, scale, dq);
     if (dk || dv) {
         if (!dk || !dv) return SP_EINVAL;
         launch(0, k_attn_dkv<D>, grid, dim3(kBlock), s, q, k, v, dout, lse, (const float*)delta,
@@ -602,9 +648,12 @@ int sp_attention_bwd_mh(const float* q, const float* k, const float* v, const fl
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t bh = batch * heads;
     const AtKV kv{static_cast<int>(m), rs_kv, kv_batch == 1 && batch > 1};
+    // shapes whose forward sp_attention_fwd_mh may have routed to the split-bf16 kernel (whatever the
+    // switch says now): dq with the consistency correction of k_attn_dq<D, true>
+    const bool corr = m == n && kv_batch == batch && rs_kv == rs && sp_attention6_supported(batch, heads, n, d);
     switch (d) {
-        case 40: return attn_bwd_d<40>(q, k, v, out, dout, lse, bh, heads, n, rs, ro, kv, scale, delta, dq, dk, dv, s);
-        case 80: return attn_bwd_d<80>(q, k, v, out, dout, lse, bh, heads, n, rs, ro, kv, scale, delta, dq, dk, dv, s);
+        case 40: return attn_bwd_d<40>(q, k, v, out, dout, lse, bh, heads, n, rs, ro, kv, scale, delta, dq, dk, dv, s, corr);
+        case 80: return attn_bwd_d<80>(q, k, v, out, dout, lse, bh, heads, n, rs, ro, kv, scale, delta, dq, dk, dv, s, corr);
         default: return attn_bwd_d<160>(q, k, v, out, dout, lse, bh, heads, n, rs, ro, kv, scale, delta, dq, dk, dv, s);
     }
 }
