@@ -5,6 +5,7 @@ ARCH  ?= gfx950
 CXXFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 SRC := samplers_amd/csrc/sp_dps.hip samplers_amd/csrc/sp_blur.hip samplers_amd/csrc/sp_sr.hip \
        samplers_amd/csrc/sp_psf.hip samplers_amd/csrc/sp_phase.hip \
+       samplers_amd/csrc/sp_psf_fft.hip \
        samplers_amd/csrc/sp_latent.hip \
        samplers_amd/csrc/sp_groupnorm.hip samplers_amd/csrc/sp_conv.hip \
        samplers_amd/csrc/sp_wino.hip samplers_amd/csrc/sp_conv_thin.hip \
@@ -33,7 +34,7 @@ build/sp_psf.o build/debug/sp_psf.o: EXTRA := -fno-slp-vectorize
 # every score / output block between the two register files around each MFMA
 build/sp_attention.o build/debug/sp_attention.o build/sp_attention6.o build/debug/sp_attention6.o build/sp_bf16.o build/debug/sp_bf16.o: EXTRA := -mllvm -amdgpu-mfma-vgpr-form=1
 
-build/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h include/samplers_hip.h
+build/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h samplers_amd/csrc/sp_fft.h include/samplers_hip.h
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) $(EXTRA) -c $< -o $@
 
@@ -41,7 +42,7 @@ $(LIB): $(OBJ)
 	@mkdir -p samplers_amd/lib
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $(OBJ)
 
-build/debug/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h include/samplers_hip.h
+build/debug/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h samplers_amd/csrc/sp_fft.h include/samplers_hip.h
 	@mkdir -p build/debug
 	$(HIPCC) $(CXXFLAGS) $(EXTRA) -DSP_DEBUG=1 -c $< -o $@
 

@@ -66,13 +66,22 @@ enum {
                            (2*radius+1)^2 taps (motion blur, defocus, measured
                            PSFs), correlation with reflect padding; adjoint =
                            exact transpose; no pseudo-inverse; m == n           */
-    SP_OP_PHASE = 6     /* new, NONLINEAR: Fourier phase retrieval,
+    SP_OP_PHASE = 6,    /* new, NONLINEAR: Fourier phase retrieval,
                            y = |FFT2(zero-pad(x))| per channel plane, norm "ortho",
                            unshifted (DC at [0][0]); pad_h = radius rows and
                            pad_w = factor columns of zeros on each side; the padded
                            sizes Nh = height + 2*radius, Nw = width + 2*factor are
                            2^k or 3*2^k in [8, 1024]; m = channels*Nh*Nw.  No
                            adjoint: sp_op_apply_ws / sp_op_vjp_ws                */
+    SP_OP_PSF_FFT = 7   /* new: the correlation of SP_OP_PSF through in-LDS FFTs, for
+                           any radius 1 <= radius <= min(height, width) - 1 with
+                           height + 2*radius, width + 2*radius <= 1024, the image
+                           extended by reflection, wrap-around or zeros (factor =
+                           0, 1, 2).  Nh (Nw) is the smallest 2^k or 3*2^k in
+                           [8, 1024] >= height + 2*radius (width + 2*radius); taps
+                           holds the PSF's SPECTRUM (below).  Linear, m == n, no
+                           pseudo-inverse; the maps need a workspace:
+                           sp_op_apply_ws = A, sp_op_vjp_ws = A^T (x not read)   */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -87,13 +96,24 @@ typedef struct sp_op {
     const int32_t* word_rank;        /* INPAINT: observed count before word w  */
     const float* taps;               /* BLUR: 2*radius+1 normalised taps.  PSF: the
                                         dense row-major (2*radius+1)^2 taps, used
-                                        as given (any finite values)            */
+                                        as given (any finite values).  PSF_FFT: the
+                                        PSF's spectrum, 2*(Nw/2+1)*Nh floats:
+                                        Hs[kw][kh] = sum_{u,v} h[u][v] *
+                                        exp(-2 pi i (u kh / Nh + v kw / Nw)) over the
+                                        (2*radius+1)^2 taps h (row u, column v),
+                                        unnormalised, computed in fp64 and rounded to
+                                        fp32, as (re, im) pairs at
+                                        taps[2*(kw*Nh + kh)], 0 <= kw <= Nw/2,
+                                        0 <= kh < Nh                             */
     int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
-                                        zero rows added above and below         */
+                                        zero rows added above and below.  PSF_FFT:
+                                        1..min(height, width) - 1               */
     int32_t factor;                  /* SR: 2, 4 or 8.  PHASE: pad_w >= 0, zero
-                                        columns added left and right (0 for the
-                                        other kinds).  PHASE: keep_bits, word_rank
-                                        and taps must be NULL                   */
+                                        columns added left and right.  PSF_FFT: the
+                                        boundary: 0 reflect, 1 circular, 2 zeros (0
+                                        for the other kinds).  PHASE: keep_bits,
+                                        word_rank and taps must be NULL; PSF_FFT:
+                                        keep_bits and word_rank                 */
 } sp_op;
 
 /* Scalars of one DPS step (all fp32, computed on the host exactly as the
@@ -172,16 +192,20 @@ int sp_debug_selftest(sp_stream_t stream);
  * height, width > 2 * radius.  PHASE: the column tiles per sample of its column launch
  * (csrc/sp_phase.hip); rejected unless radius, factor >= 0, both padded sizes are 2^k or 3*2^k in
  * [8, 1024], n == channels*height*width, m == channels*Nh*Nw and keep_bits, word_rank and taps
- * are NULL. */
+ * are NULL.  PSF_FFT: the row tiles per sample of its fused rows^-1 + rows launch
+ * (csrc/sp_psf_fft.hip); rejected unless taps != NULL, factor is 0, 1 or 2,
+ * 1 <= radius <= min(height, width) - 1, height + 2*radius <= 1024, width + 2*radius <= 1024,
+ * m == n == channels*height*width and keep_bits and word_rank are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
 /* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
  * 0 for every kind but PSF (one pass, no workspace), batch * m for PSF (its residual launch
  * leaves grad_scale * r there for the adjoint launch), 2 * batch * channels * Nw * height for
- * PHASE (the complex row transforms, stored transposed).  SP_EINVAL for a rejected descriptor
- * or batch <= 0.  The library allocates nothing. */
+ * PHASE (the complex row transforms, stored transposed), 2 * batch * channels * (Nw/2 + 1) * height
+ * for PSF_FFT (the same, half the spectrum: the rows are real).  SP_EINVAL for a rejected
+ * descriptor or batch <= 0.  The library allocates nothing. */
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
 /* Floats of `work` that sp_op_apply_ws / sp_op_vjp_ws need: 0 for the linear kinds, the figure
- * of sp_dps_workspace for PHASE.  SP_EINVAL for a rejected descriptor or batch <= 0. */
+ * of sp_dps_workspace for PHASE and PSF_FFT.  SP_EINVAL for a rejected descriptor or batch <= 0. */
 int64_t sp_op_workspace(const sp_op* op, int64_t batch);
 
 /* What the kind of `op` does at the entry points below, as bits; 0 for a rejected descriptor.
@@ -214,6 +238,11 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  * (csrc/sp_phase.hip): row FFTs of x0 -> work; per column tile the forward column FFT,
  * r = y - |z|, one r^2 partial, u = grad_scale * r * z/|z| (0 at |z| = 0) and the inverse column
  * FFT, in LDS, back into work; inverse row FFTs, real part, crop -> v = J(x0)^T(grad_scale * r).
+ * PSF_FFT runs here only as well, as five launches (csrc/sp_psf_fft.hip): row FFTs of the extended
+ * x0 -> work; per column tile the forward column FFT, times conj(spectrum), inverse column FFT;
+ * per row tile the inverse row FFT, g = grad_scale * (y - A x0), one r^2 partial and the forward
+ * row FFT of g; the column launch again with the spectrum and the fold; inverse row FFTs and the
+ * fold -> v = A^T g.
  * work must not alias any other argument. */
 int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
                        int64_t batch, int64_t y_div, const sp_dps_coefs* c,
@@ -224,7 +253,7 @@ int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const 
  *   g   = v/a - (k/a) * w          (w = J_eps^T v from the prior's VJP)
  *   x'  = c_ell*x + c_s*x0 + std*xi + gamma/(sqrt(sum_p rsq_partial[b][p]) + norm_eps) * g
  * v: pass NULL to recompute v from (x, eps, y) (IDENTITY/INPAINT/MASK), else
- *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF and PHASE, which run the
+ *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF, PHASE and PSF_FFT, which run the
  *    identity-kind update over it: the Philox element index stays the flat element index).
  * rsq_partial: NULL selects a fixed factor, x' = ... + gamma * g — the PGDM update
  *    (pgdm.py:126-135, gamma = -guidance_weight*sqrt(1-acp_t), v = -2 A^T r) and the
@@ -259,12 +288,14 @@ int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_str
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream);
 /* y = A(x) with a workspace of sp_op_workspace floats: sp_op_apply for the linear kinds (work
  * unused, may be NULL); PHASE: y = |FFT2(pad(x))| (sp_op_apply and sp_op_adjoint return
- * SP_EUNSUPPORTED for PHASE, as do sp_psld_pixel, sp_psld_cotangent and sp_pixel_opt_step). */
+ * SP_EUNSUPPORTED for PHASE, as do sp_psld_pixel, sp_psld_cotangent and sp_pixel_opt_step);
+ * PSF_FFT: y = A x, the extended correlation (the same entries return SP_EUNSUPPORTED for it). */
 int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
                    sp_stream_t stream);
 /* dx = J(x)^T g for the nonlinear kinds (g: batch rows of m, dx: batch rows of n).  PHASE:
  * crop(Re(IFFT2(g * z/|z|))) with z = FFT2(pad(x)) recomputed, z/|z| = 0 at |z| = 0 (never NaN
- * or inf).  SP_EUNSUPPORTED for the linear kinds, whose VJP is sp_op_adjoint. */
+ * or inf).  PSF_FFT: dx = A^T g, the exact adjoint (x is not read).  SP_EUNSUPPORTED for the
+ * linear kinds without a workspace, whose VJP is sp_op_adjoint. */
 int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
                  float* work, sp_stream_t stream);
 

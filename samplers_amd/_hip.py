@@ -19,6 +19,7 @@ DEBUG_LIB_PATH = Path(__file__).resolve().parent / "lib" / "debug" / "libsampler
 
 SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR, SP_OP_PSF = 0, 1, 2, 3, 4, 5
 SP_OP_PHASE = 6  # nonlinear: sp_op_apply_ws / sp_op_vjp_ws, no adjoint
+SP_OP_PSF_FFT = 7  # linear through a workspace: sp_op_apply_ws = A, sp_op_vjp_ws = A^T
 # sp_op_traits bits: what a kind does at the entry points (the library's table, not a list here)
 SP_TRAIT_UPDATE_READS_V, SP_TRAIT_DPS_WORKSPACE, SP_TRAIT_FUSED_LATENT = 1, 2, 4
 SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U = 8, 16

@@ -457,11 +457,17 @@ static const op_kind g_kinds[] = {
     {phase_valid, phase_partials, phase_workspace, phase_workspace, phase_dps_residual, nullptr,
      nullptr, phase_apply, phase_vjp, nullptr, nullptr, nullptr,
      SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
+    /* SP_OP_PSF_FFT: linear, but its maps need the workspace: apply_ws = A, vjp_ws = A^T (x not
+       read); five pass-1 launches through work; no sp_op_apply / _adjoint, no latent passes */
+    {psf_fft_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace, psf_fft_dps_residual,
+     nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr, nullptr, nullptr,
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
 };
 #undef SP_ELEMENTWISE_ROW
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
-                  SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && kKinds == 7,
+                  SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
+                  kKinds == 8,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -479,7 +485,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 105; }
+int sp_version(void) { return 106; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 

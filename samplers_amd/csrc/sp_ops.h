@@ -45,7 +45,7 @@ struct op_kind {
     workspace_fn *dps_workspace, *op_workspace;
     dps_residual_fn* dps_residual;
     map_fn *apply, *adjoint;  // the linear kinds
-    apply_ws_fn* apply_ws;    // the nonlinear kinds (with vjp_ws)
+    apply_ws_fn* apply_ws;    // the kinds whose maps need a workspace (with vjp_ws)
     vjp_ws_fn* vjp_ws;
     psld_pixel_fn* psld_pixel;
     psld_cotangent_fn* psld_cotangent;
@@ -58,14 +58,15 @@ bool valid_op(const sp_op* op);
 int64_t tiles_elementwise(int64_t n);
 
 // the kinds' functions, one line per column of the table (sp_blur.hip, sp_sr.hip, sp_psf.hip,
-// sp_phase.hip; elementwise_*: sp_latent.hip, the cotangent serves BLUR and PSF over A^T A u too)
-valid_fn blur_valid, sr_valid, psf_valid, phase_valid;
-partials_fn blur_partials, sr_partials, psf_partials, phase_partials;
-workspace_fn psf_workspace, phase_workspace;
-dps_residual_fn blur_dps_residual, sr_dps_residual, psf_dps_residual, phase_dps_residual;
+// sp_phase.hip, sp_psf_fft.hip; elementwise_*: sp_latent.hip, the cotangent serves BLUR and PSF over A^T A u too)
+valid_fn blur_valid, sr_valid, psf_valid, phase_valid, psf_fft_valid;
+partials_fn blur_partials, sr_partials, psf_partials, phase_partials, psf_fft_partials;
+workspace_fn psf_workspace, phase_workspace, psf_fft_workspace;
+dps_residual_fn blur_dps_residual, sr_dps_residual, psf_dps_residual, phase_dps_residual,
+    psf_fft_dps_residual;
 map_fn blur_apply, blur_adjoint, sr_apply, sr_adjoint, psf_apply, psf_adjoint;
-apply_ws_fn phase_apply;
-vjp_ws_fn phase_vjp;
+apply_ws_fn phase_apply, psf_fft_apply;
+vjp_ws_fn phase_vjp, psf_fft_vjp;
 psld_pixel_fn elementwise_psld_pixel, sr_psld_pixel;
 psld_cotangent_fn elementwise_psld_cotangent, sr_psld_cotangent;
 pixel_opt_fn elementwise_pixel_opt, sr_pixel_opt;

@@ -1,0 +1,413 @@
+// FFT-domain point-spread-function blur (SP_OP_PSF_FFT): the correlation of SP_OP_PSF,
+//   y[c,i,j] = sum_{u,v} h[u,v] xe[c, i+u, j+v],  0 <= u, v < K = 2R + 1,
+// with xe the image extended by R on each side by reflection, wrap-around or zeros
+// (op.factor = 0, 1, 2), evaluated through circular transforms of Nh x Nw points, Nh (Nw) the
+// smallest 2^k or 3 * 2^k in [8, 1024] that holds H + 2R (W + 2R).  Semantics in
+// operators/psf_fft.py, pinned in fp64 by tests/psf_fft_ops.py.  With xe at [0, H+2R) x [0, W+2R)
+// of a zero Nh x Nw array and Hs = FFT2 of h at [0, K) x [0, K) (op.taps, the caller's):
+//   A x   = IFFT2(FFT2(xe) * conj(Hs)) [0, H) x [0, W)          (no index wraps: i + u < Nh)
+//   A^T g = fold(IFFT2(FFT2(g at [0, H) x [0, W)) * Hs) [0, H+2R) x [0, W+2R))
+// where fold is the transpose of the extension: every extended position is added onto the pixel
+// it was copied from (zeros: the margin is dropped).
+//
+// Three launches through the caller's workspace, as SP_OP_PHASE (sp_phase.hip), with the FFT core
+// of sp_fft.h:
+//   1. rows     a workgroup stages TR rows of one plane (x0 = (x - k eps) / a in DPS form),
+//               extended W -> W + 2R by the mode's index function (A) or as they are (A^T),
+//               zero-extended to Nw; Nw-point FFT per row; columns kw <= Nw / 2 stored TRANSPOSED
+//               (the rows are real: the other half is the conjugate mirror).
+//   2. columns  a workgroup loads TC columns of H values, extends H -> H + 2R by the same index
+//               function in LDS (A; the row transform is linear, so extending the rows after it is
+//               exact), zero-extends to Nh; forward FFT; times conj(Hs) / (Nh Nw) (A) or
+//               Hs / (Nh Nw) (A^T); inverse FFT; rows 0 .. H-1 (A) or positions 0 .. H+2R-1 folded
+//               onto the H rows (A^T) stored back over the columns it loaded.
+//   3. rows^-1  TR rows of the intermediate -> LDS, kw > Nw / 2 rebuilt by conjugate symmetry,
+//               inverse FFT, real part; columns 0 .. W-1 (A) or 0 .. W+2R-1 folded onto W (A^T).
+// DPS pass 1 is five launches: rows, columns (A), rows^-1 fused with rows (the block holds the
+// rows of A x0 in LDS, forms g = grad_scale (y - A x0) and its r^2 partial, zero-extends g and
+// transforms it forward again in place), columns (A^T), rows^-1 (A^T) -> v.
+//
+// Intermediate: complex fp32 (re, im), [sample][plane][Nw / 2 + 1][H];
+// 2 * batch * C * (Nw / 2 + 1) * H floats.  Spectrum (op.taps): (re, im) pairs [Nw / 2 + 1][Nh],
+// so a column tile reads one contiguous run.
+//
+// A fold adds its at most three terms in a fixed order: interior, low-border image, high-border
+// image (1 <= R <= min(H, W) - 1 bounds the pre-images per axis by three).  Every sample is
+// computed alone, lines are assigned by plane and tile only, the r^2 partial of a
+// (plane, row tile) is block_sum's fixed order: the bits do not depend on the batch, y_div or the
+// shard.  Plain stores, no atomics.
+
+#include <algorithm>
+
+#define SP_TU 18  // debug-build site numbering (sp_common.h SP_DCHECK)
+#include "sp_ops.h"
+#include "sp_fft.h"
+
+namespace sp {
+
+enum { PF_REFLECT = 0, PF_CIRCULAR = 1, PF_ZEROS = 2 };
+enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2 };
+
+// smallest 2^k or 3 * 2^k in [8, 1024] that is >= n; 0 if there is none
+static int pf_size(int n) {
+    for (int N = n < 8 ? 8 : n; N <= 1024; ++N)
+        if (phase_size_ok(N)) return N;
+    return 0;
+}
+
+struct pf_geom {  // filled on the host from a valid descriptor
+    int C, H, W, R, mode, Nh, Nw, HW;  // HW = Nw / 2 + 1 stored columns
+    const float2* spec;                // [HW][Nh]
+};
+
+static pf_geom pf_geometry(const sp_op* op) {
+    pf_geom g;
+    g.C = op->channels, g.H = op->height, g.W = op->width, g.R = op->radius, g.mode = op->factor;
+    g.Nh = pf_size(op->height + 2 * op->radius);
+    g.Nw = pf_size(op->width + 2 * op->radius);
+    g.HW = g.Nw / 2 + 1;
+    g.spec = reinterpret_cast<const float2*>(op->taps);
+    return g;
+}
+
+// source pixel of extended position p in [0, n + 2R) along an axis of n pixels; -1: a zero
+__device__ __forceinline__ int pf_src(int p, int R, int n, int mode) {
+    const int i = p - R;
+    if (i >= 0 && i < n) return i;
+    if (mode == PF_ZEROS) return -1;
+    if (mode == PF_REFLECT) return i < 0 ? -i : 2 * (n - 1) - i;
+    return i < 0 ? i + n : i - n;
+}
+
+// the extended positions besides R + i that pf_src maps to pixel i: one in the low border
+// [0, R), one in the high border [n + R, n + 2R), -1 where there is none
+__device__ __forceinline__ void pf_images(int i, int R, int n, int mode, int& lo, int& hi) {
+    lo = hi = -1;
+    if (mode == PF_REFLECT) {
+        if (i >= 1 && i <= R) lo = R - i;
+        if (i >= n - 1 - R && i <= n - 2) hi = R + 2 * (n - 1) - i;
+    } else if (mode == PF_CIRCULAR) {
+        if (i >= n - R) lo = R + i - n;
+        if (i < R) hi = R + i + n;
+    }
+}
+
+// launch 1.  X0: x0 = (in - k eps) / a while staging.  EXT: extend by the mode (A), else the row
+// as it is at [0, W) (A^T).
+template <bool X0, bool EXT>
+__global__ __launch_bounds__(kBlock) void k_pf_rows(pf_geom g, const float* __restrict__ in,
+                                                    const float* __restrict__ eps, float a, float k,
+                                                    float2* __restrict__ ws, int T,
+                                                    const sp_step_rec* __restrict__ sched,
+                                                    const int32_t* __restrict__ cursor) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (X0 && sched) {  // device-resident schedule (graph replay)
+        const sp_dps_coefs& cf = sched[*cursor].c;
+        a = cf.a, k = cf.k;
+    }
+    const int N = g.Nw, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.H + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int h0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    SP_DCHECK(c < g.C && h0 < g.H);
+    const float* __restrict__ ip = in + plane * g.H * g.W;
+    const float* __restrict__ ep = X0 ? eps + plane * g.H * g.W : nullptr;
+    const int ext = EXT ? g.W + 2 * g.R : g.W;
+
+    phase_twiddles(tw, N);
+    for (int t = 0; t < T; ++t) {
+        const int h = h0 + t;
+        for (int q = threadIdx.x; q < N; q += kBlock) {
+            float val = 0.f;
+            const int j = q < ext ? (EXT ? pf_src(q, g.R, g.W, g.mode) : q) : -1;
+            if (h < g.H && j >= 0) {
+                SP_DCHECK(j < g.W && h * g.W + j < g.H * g.W);
+                val = ip[h * g.W + j];
+                if constexpr (X0) val = (val - k * ep[h * g.W + j]) / a;
+            }
+            A[t * NP + phase_slot(q)] = make_float2(val, 0.f);
+        }
+    }
+    __syncthreads();
+    const float2* res = phase_fft(A, B, tw, N, NP, T, false);
+    // transposed store of the half spectrum: ws[plane][kw][h], the tile's rows adjacent
+    float2* __restrict__ wp = ws + plane * (int64_t)g.HW * g.H;
+    const int total = T * g.HW;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, h = h0 + t;
+        if (h < g.H) {
+            SP_DCHECK(kw < g.HW && kw * g.H + h < g.HW * g.H);
+            wp[kw * g.H + h] = res[t * NP + phase_slot(kw)];
+        }
+    }
+}
+
+// launch 2.  ADJ false: A (extend, conj(Hs), keep rows 0 .. H-1); true: A^T (Hs, fold).
+template <bool ADJ>
+__global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restrict__ ws, int T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int N = g.Nh, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.HW + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int kw0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    SP_DCHECK(c < g.C && kw0 < g.HW);
+    float2* __restrict__ wp = ws + (plane * g.HW + kw0) * (int64_t)g.H;  // the tile's columns
+    const int lines = min(T, g.HW - kw0);
+    const int ext = ADJ ? g.H : g.H + 2 * g.R;
+
+    phase_twiddles(tw, N);
+    for (int t = 0; t < T; ++t)
+        for (int q = threadIdx.x; q < N; q += kBlock) {
+            float2 val = make_float2(0.f, 0.f);
+            const int h = q < ext ? (ADJ ? q : pf_src(q, g.R, g.H, g.mode)) : -1;
+            if (t < lines && h >= 0) {
+                SP_DCHECK(h < g.H);
+                val = wp[t * g.H + h];
+            }
+            A[t * NP + phase_slot(q)] = val;
+        }
+    __syncthreads();
+    float2* z = phase_fft(A, B, tw, N, NP, T, false);
+
+    // times the PSF's spectrum (its conjugate for the correlation) and both inverse transforms'
+    // 1 / (Nh Nw); the spectrum's columns are contiguous
+    const float s = 1.f / ((float)g.Nh * (float)g.Nw);
+    const float2* __restrict__ hsp = g.spec + (int64_t)kw0 * N;
+    const int total = lines * N;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int t = idx / N, kh = idx - t * N;
+        SP_DCHECK(t < lines && kw0 + t < g.HW);
+        float2 hs = hsp[idx];
+        hs.x *= s;
+        hs.y *= ADJ ? s : -s;
+        float2* zp = z + t * NP + phase_slot(kh);
+        *zp = cmul(*zp, hs);
+    }
+    __syncthreads();
+    const float2* u = phase_fft(z, z == A ? B : A, tw, N, NP, T, true);
+    const int keep = lines * g.H;
+    for (int idx = threadIdx.x; idx < keep; idx += kBlock) {
+        const int t = idx / g.H, h = idx - t * g.H;
+        const float2* ul = u + t * NP;
+        float2 val;
+        if constexpr (ADJ) {
+            int lo, hi;
+            pf_images(h, g.R, g.H, g.mode, lo, hi);
+            SP_DCHECK(g.R + h < N && lo < g.R && (hi < 0 || (hi >= g.H + g.R && hi < g.H + 2 * g.R)));
+            val = ul[phase_slot(g.R + h)];
+            if (lo >= 0) val = cadd(val, ul[phase_slot(lo)]);
+            if (hi >= 0) val = cadd(val, ul[phase_slot(hi)]);
+        } else {
+            val = ul[phase_slot(h)];
+        }
+        wp[idx] = val;
+    }
+}
+
+// launch 3.  OUT: PF_OUT_A columns 0 .. W-1 -> out; PF_OUT_AT columns 0 .. W+2R-1 folded onto W
+// -> out; PF_OUT_RESIDUAL the fused launch of DPS pass 1: g = gs (y - A x0) and the r^2 partial
+// of the tile, then the forward row transform of g back into the intermediate.
+template <int OUT>
+__global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __restrict__ ws,
+                                                        float* __restrict__ out,
+                                                        const float* __restrict__ y, int64_t y_div,
+                                                        float gs, float* __restrict__ partial, int P,
+                                                        int T, const sp_step_rec* __restrict__ sched,
+                                                        const int32_t* __restrict__ cursor) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[4];
+    if (OUT == PF_OUT_RESIDUAL && sched) gs = sched[*cursor].c.grad_scale;
+    const int N = g.Nw, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.H + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int h0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t b = blockIdx.y;
+    const int64_t plane = b * g.C + c;
+    SP_DCHECK(c < g.C && h0 < g.H && (OUT != PF_OUT_RESIDUAL || static_cast<int>(blockIdx.x) < P));
+    float2* __restrict__ wp = ws + plane * (int64_t)g.HW * g.H;
+
+    phase_twiddles(tw, N);
+    const int total = T * g.HW;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, h = h0 + t;
+        float2 val = make_float2(0.f, 0.f);
+        if (h < g.H) {
+            SP_DCHECK(kw < g.HW && kw * g.H + h < g.HW * g.H);
+            val = wp[kw * g.H + h];
+        }
+        A[t * NP + phase_slot(kw)] = val;
+        if (kw > 0 && 2 * kw < N) {  // the spectrum of a real row: X[N - kw] = conj(X[kw])
+            SP_DCHECK(N - kw >= g.HW && N - kw < N);
+            A[t * NP + phase_slot(N - kw)] = make_float2(val.x, -val.y);
+        }
+    }
+    __syncthreads();
+    float2* res = phase_fft(A, B, tw, N, NP, T, true);
+
+    if constexpr (OUT == PF_OUT_RESIDUAL) {
+        const int64_t yplane = (b / y_div) * g.C + c;
+        const float* __restrict__ yp = y + yplane * g.H * g.W;
+        float racc = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const int h = h0 + t;
+            // every element is read and rewritten by the one thread that owns it
+            for (int q = threadIdx.x; q < N; q += kBlock) {
+                float gv = 0.f;
+                float2* rp = res + t * NP + phase_slot(q);
+                if (h < g.H && q < g.W) {
+                    SP_DCHECK(h * g.W + q < g.H * g.W);
+                    const float r = yp[h * g.W + q] - rp->x;
+                    racc += r * r;
+                    gv = gs * r;
+                }
+                *rp = make_float2(gv, 0.f);
+            }
+        }
+        const float tsum = block_sum(racc, red);  // its barrier also orders the rewritten rows
+        if (threadIdx.x == 0) partial[b * P + blockIdx.x] = tsum;
+        __syncthreads();
+        const float2* f = phase_fft(res, res == A ? B : A, tw, N, NP, T, false);
+        for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int kw = idx / T, t = idx - kw * T, h = h0 + t;
+            if (h < g.H) {
+                SP_DCHECK(kw < g.HW && kw * g.H + h < g.HW * g.H);
+                wp[kw * g.H + h] = f[t * NP + phase_slot(kw)];
+            }
+        }
+    } else {
+        float* __restrict__ op_out = out + plane * g.H * g.W;
+        for (int t = 0; t < T; ++t) {
+            const int h = h0 + t;
+            if (h >= g.H) break;
+            const float2* rl = res + t * NP;
+            for (int j = threadIdx.x; j < g.W; j += kBlock) {
+                SP_DCHECK(h * g.W + j < g.H * g.W);
+                float val;
+                if constexpr (OUT == PF_OUT_AT) {
+                    int lo, hi;
+                    pf_images(j, g.R, g.W, g.mode, lo, hi);
+                    SP_DCHECK(g.R + j < N && lo < g.R &&
+                              (hi < 0 || (hi >= g.W + g.R && hi < g.W + 2 * g.R)));
+                    val = rl[phase_slot(g.R + j)].x;
+                    if (lo >= 0) val += rl[phase_slot(lo)].x;
+                    if (hi >= 0) val += rl[phase_slot(hi)].x;
+                } else {
+                    val = rl[phase_slot(j)].x;
+                }
+                op_out[h * g.W + j] = val;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side (called from the entry points in sp_dps.hip; `op` is valid)
+// ---------------------------------------------------------------------------
+bool psf_fft_valid(const sp_op* op) {  // radius = R, factor = padding mode, taps = the spectrum
+    if (!op->taps || op->keep_bits || op->word_rank || op->factor < 0 || op->factor > 2 ||
+        op->channels <= 0 || op->height <= 0 || op->width <= 0 || op->radius < 1 ||
+        op->radius > std::min(op->height, op->width) - 1 || op->height > 1024 || op->width > 1024 ||
+        op->height + 2 * op->radius > 1024 || op->width + 2 * op->radius > 1024)
+        return false;
+    return (int64_t)op->channels * op->height * op->width == op->n && op->m == op->n &&
+           phase_size_ok(pf_size(op->height + 2 * op->radius)) &&
+           phase_size_ok(pf_size(op->width + 2 * op->radius));
+}
+
+static inline int pf_row_tiles(const pf_geom& g) {
+    const int T = phase_lines(g.Nw);
+    return (g.H + T - 1) / T;
+}
+static inline int pf_col_tiles(const pf_geom& g) {
+    const int T = phase_lines(g.Nh);
+    return (g.HW + T - 1) / T;
+}
+
+// row tiles per sample = workgroups per sample of the fused launch = r^2 partials per sample
+int64_t psf_fft_partials(const sp_op* op) {
+    return (int64_t)op->channels * pf_row_tiles(pf_geometry(op));
+}
+
+// floats of the intermediate
+int64_t psf_fft_workspace(const sp_op* op, int64_t batch) {
+    const pf_geom g = pf_geometry(op);
+    return 2 * batch * g.C * (int64_t)g.HW * g.H;
+}
+
+static const sp_step_rec* const kNoSched = nullptr;
+static const int32_t* const kNoCursor = nullptr;
+
+// rows, columns, rows^-1 of A (ADJ false) or A^T (true): in -> work -> out
+template <bool ADJ>
+static int pf_map(const char* what, const sp_op* op, const float* in, float* out, int64_t batch,
+                  float* work, hipStream_t s) {
+    const pf_geom g = pf_geometry(op);
+    float2* ws = reinterpret_cast<float2*>(work);
+    const dim3 rows = sample_grid(g.C * pf_row_tiles(g), batch);
+    launch_w(0, 0.0, k_pf_rows<false, !ADJ>, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, g, in,
+             (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), kNoSched, kNoCursor);
+    int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(0, 0.0, k_pf_cols<ADJ>, sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock),
+             phase_lds_bytes(g.Nh), s, g, ws, phase_lines(g.Nh));
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(0, 0.0, k_pf_rows_inv<ADJ ? PF_OUT_AT : PF_OUT_A>, rows, dim3(kBlock),
+             phase_lds_bytes(g.Nw), s, g, ws, out, (const float*)nullptr, (int64_t)1, 0.f,
+             (float*)nullptr, 0, phase_lines(g.Nw), kNoSched, kNoCursor);
+    return check_launch(what);
+}
+
+int psf_fft_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                  hipStream_t s) {
+    return pf_map<false>("sp_op_apply_ws", op, x, y, batch, work, s);
+}
+
+// the map is linear: A^T gy, x is not read
+int psf_fft_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
+                float* work, hipStream_t s) {
+    (void)x;
+    return pf_map<true>("sp_op_vjp_ws", op, gy, dx, batch, work, s);
+}
+
+// rows (x, eps -> work), columns A, rows^-1 + rows (work, y -> work, partials), columns A^T,
+// rows^-1 A^T (work -> v)
+int psf_fft_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    const pf_geom g = pf_geometry(op);
+    float2* ws = reinterpret_cast<float2*>(r.work);
+    const int P = static_cast<int>(psf_fft_partials(op));
+    const int TR = phase_lines(g.Nw), TC = phase_lines(g.Nh);
+    const size_t lr = phase_lds_bytes(g.Nw), lc = phase_lds_bytes(g.Nh);
+    const dim3 rows = sample_grid(P, r.batch), cols = sample_grid(g.C * pf_col_tiles(g), r.batch);
+    const char* what = "sp_dps_residual_ws";
+    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_pf_rows<true, true>, rows, dim3(kBlock), lr, s, g,
+             r.x, r.eps, r.a, r.k, ws, TR, r.sched, r.cursor);
+    int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false>, cols, dim3(kBlock), lc, s, g, ws, TC);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, rows, dim3(kBlock), lr, s, g, ws,
+             (float*)nullptr, r.y, r.y_div, r.gs, r.partial, P, TR, r.sched, r.cursor);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<true>, cols, dim3(kBlock), lc, s, g, ws, TC);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_AT>, rows, dim3(kBlock), lr, s, g, ws, r.v,
+             (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, TR, kNoSched, kNoCursor);
+    return check_launch(what);
+}
+
+}  // namespace sp

@@ -14,6 +14,7 @@ from .inpainting import (
 from .phase import PhaseRetrievalOperator
 from .linear import GeneralSVDOperator, LinearOperator, SVDOperator
 from .psf import MotionBlurOperator, PSFBlurOperator, motion_blur_kernel
+from .psf_fft import FFTPSFBlurOperator, padded_size, psf_spectrum
 from .superres import SuperResolutionOperator
 
 __all__ = [
@@ -32,8 +33,11 @@ __all__ = [
     "SuperResolutionOperator",
     "PSFBlurOperator",
     "MotionBlurOperator",
+    "FFTPSFBlurOperator",
     "PhaseRetrievalOperator",
     "motion_blur_kernel",
+    "padded_size",
+    "psf_spectrum",
     "get_mask_inpaint_center",
     "get_mask_side_painting",
     "get_mask_random",

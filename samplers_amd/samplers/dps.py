@@ -130,8 +130,8 @@ class FusedDPSStep:
             raise NotImplementedError(
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
-                "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses) and "
-                "PhaseRetrievalOperator"
+                "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses), "
+                "FFTPSFBlurOperator and PhaseRetrievalOperator"
             )
         _hip.require_cuda(observation_rows, "DPSSampler")
         if observation_rows.dtype != torch.float32:
@@ -151,8 +151,8 @@ class FusedDPSStep:
             raise ValueError(mode)
         self.traits = int(self.lib.sp_op_traits(desc))
         if mode == "pgdm" and not self.traits & _hip.SP_TRAIT_LINEAR:
-            raise NotImplementedError(f"{type(op).__name__} is nonlinear and has no "
-                                      "apply_pseudo_inverse: PGDM does not apply")
+            raise NotImplementedError(f"{type(op).__name__} has no apply_pseudo_inverse (nonlinear, "
+                                      "or a blur through a workspace): PGDM does not apply")
         self.mode = mode
         # DPS: d log p/d(Ax) = c r.  PGDM: d/dx0 of ||A^+ y - A^+ A x0||^2 = -c A^T r with the
         # operator's pinv_grad_scale c: 2 for the partial isometries (A^+ = A^T: identity,
