@@ -73,7 +73,7 @@ enum {
                            sizes Nh = height + 2*radius, Nw = width + 2*factor are
                            2^k or 3*2^k in [8, 1024]; m = channels*Nh*Nw.  No
                            adjoint: sp_op_apply_ws / sp_op_vjp_ws                */
-    SP_OP_PSF_FFT = 7   /* new: the correlation of SP_OP_PSF through in-LDS FFTs, for
+    SP_OP_PSF_FFT = 7,  /* new: the correlation of SP_OP_PSF through in-LDS FFTs, for
                            any radius 1 <= radius <= min(height, width) - 1 with
                            height + 2*radius, width + 2*radius <= 1024, the image
                            extended by reflection, wrap-around or zeros (factor =
@@ -82,6 +82,15 @@ enum {
                            holds the PSF's SPECTRUM (below).  Linear, m == n, no
                            pseudo-inverse; the maps need a workspace:
                            sp_op_apply_ws = A, sp_op_vjp_ws = A^T (x not read)   */
+    SP_OP_PSF_PERIODIC = 8 /* new: the wrap-around correlation of a (2*radius+1)^2 PSF on
+                           an image whose own sizes are transform lengths: height and
+                           width each 2^k or 3*2^k in [8, 1024], radius >= 1,
+                           2*radius+1 <= min(height, width), factor = 0.  The map is
+                           diagonal in the H x W transform, A = IFFT2 M FFT2, so it has
+                           a spectral pseudo-inverse; taps holds M and P (below).
+                           Linear, m == n; sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
+                           sp_op_pinv_ws = A^+ / A^+T, sp_pgdm_prepare and
+                           sp_pgdm_residual_ws the fused PGDM pass 1             */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -104,16 +113,26 @@ typedef struct sp_op {
                                         unnormalised, computed in fp64 and rounded to
                                         fp32, as (re, im) pairs at
                                         taps[2*(kw*Nh + kh)], 0 <= kw <= Nw/2,
-                                        0 <= kh < Nh                             */
+                                        0 <= kh < Nh.  PSF_PERIODIC: two such half
+                                        spectra back to back with Nh = height,
+                                        Nw = width, 2*2*(width/2+1)*height floats:
+                                        first M = conj(FFT2 of h with its centre tap
+                                        at [0][0], tap (u, v) at ((u-R) mod H,
+                                        (v-R) mod W)), the multiplier of A; then
+                                        P = 1/M on the kept frequencies and 0 on the
+                                        others, the multiplier of A^+.  P must be
+                                        conjugate-symmetric under k -> -k like M (a
+                                        symmetric kept set)                      */
     int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
                                         zero rows added above and below.  PSF_FFT:
-                                        1..min(height, width) - 1               */
+                                        1..min(height, width) - 1.  PSF_PERIODIC:
+                                        1..(min(height, width) - 1) / 2          */
     int32_t factor;                  /* SR: 2, 4 or 8.  PHASE: pad_w >= 0, zero
                                         columns added left and right.  PSF_FFT: the
                                         boundary: 0 reflect, 1 circular, 2 zeros (0
                                         for the other kinds).  PHASE: keep_bits,
-                                        word_rank and taps must be NULL; PSF_FFT:
-                                        keep_bits and word_rank                 */
+                                        word_rank and taps must be NULL; PSF_FFT
+                                        and PSF_PERIODIC: keep_bits and word_rank */
 } sp_op;
 
 /* Scalars of one DPS step (all fp32, computed on the host exactly as the
@@ -195,17 +214,21 @@ int sp_debug_selftest(sp_stream_t stream);
  * are NULL.  PSF_FFT: the row tiles per sample of its fused rows^-1 + rows launch
  * (csrc/sp_psf_fft.hip); rejected unless taps != NULL, factor is 0, 1 or 2,
  * 1 <= radius <= min(height, width) - 1, height + 2*radius <= 1024, width + 2*radius <= 1024,
+ * m == n == channels*height*width and keep_bits and word_rank are NULL.  PSF_PERIODIC: the same
+ * count with Nw = width; rejected unless taps != NULL, factor == 0, height and width are each 2^k
+ * or 3*2^k in [8, 1024], radius >= 1, 2*radius + 1 <= min(height, width),
  * m == n == channels*height*width and keep_bits and word_rank are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
 /* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
  * 0 for every kind but PSF (one pass, no workspace), batch * m for PSF (its residual launch
  * leaves grad_scale * r there for the adjoint launch), 2 * batch * channels * Nw * height for
  * PHASE (the complex row transforms, stored transposed), 2 * batch * channels * (Nw/2 + 1) * height
- * for PSF_FFT (the same, half the spectrum: the rows are real).  SP_EINVAL for a rejected
+ * for PSF_FFT (the same, half the spectrum: the rows are real) and for PSF_PERIODIC (Nw = width).  SP_EINVAL for a rejected
  * descriptor or batch <= 0.  The library allocates nothing. */
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
 /* Floats of `work` that sp_op_apply_ws / sp_op_vjp_ws need: 0 for the linear kinds, the figure
- * of sp_dps_workspace for PHASE and PSF_FFT.  SP_EINVAL for a rejected descriptor or batch <= 0. */
+ * of sp_dps_workspace for PHASE, PSF_FFT and PSF_PERIODIC (sp_op_pinv_ws and
+ * sp_pgdm_residual_ws take the same).  SP_EINVAL for a rejected descriptor or batch <= 0. */
 int64_t sp_op_workspace(const sp_op* op, int64_t batch);
 
 /* What the kind of `op` does at the entry points below, as bits; 0 for a rejected descriptor.
@@ -215,7 +238,8 @@ enum {
     SP_TRAIT_DPS_WORKSPACE = 2,  /* sp_dps_workspace > 0: pass 1 runs in the _ws forms only    */
     SP_TRAIT_FUSED_LATENT = 4,   /* sp_psld_pixel and sp_pixel_opt_step exist for the kind     */
     SP_TRAIT_LINEAR = 8,         /* sp_op_apply / sp_op_adjoint exist (else _apply_ws/_vjp_ws) */
-    SP_TRAIT_NEEDS_ATA_U = 16    /* sp_psld_cotangent requires ata_u                           */
+    SP_TRAIT_NEEDS_ATA_U = 16,   /* sp_psld_cotangent requires ata_u                           */
+    SP_TRAIT_PINV = 32           /* sp_op_pinv_ws, sp_pgdm_prepare, sp_pgdm_residual_ws exist  */
 };
 uint32_t sp_op_traits(const sp_op* op);
 
@@ -242,7 +266,8 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  * x0 -> work; per column tile the forward column FFT, times conj(spectrum), inverse column FFT;
  * per row tile the inverse row FFT, g = grad_scale * (y - A x0), one r^2 partial and the forward
  * row FFT of g; the column launch again with the spectrum and the fold; inverse row FFTs and the
- * fold -> v = A^T g.
+ * fold -> v = A^T g.  PSF_PERIODIC: the same five launches on exact-size transforms (Nh = height,
+ * Nw = width), nothing extended or folded.
  * work must not alias any other argument. */
 int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
                        int64_t batch, int64_t y_div, const sp_dps_coefs* c,
@@ -253,7 +278,7 @@ int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const 
  *   g   = v/a - (k/a) * w          (w = J_eps^T v from the prior's VJP)
  *   x'  = c_ell*x + c_s*x0 + std*xi + gamma/(sqrt(sum_p rsq_partial[b][p]) + norm_eps) * g
  * v: pass NULL to recompute v from (x, eps, y) (IDENTITY/INPAINT/MASK), else
- *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF, PHASE and PSF_FFT, which run the
+ *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF, PHASE, PSF_FFT and PSF_PERIODIC, which run the
  *    identity-kind update over it: the Philox element index stays the flat element index).
  * rsq_partial: NULL selects a fixed factor, x' = ... + gamma * g — the PGDM update
  *    (pgdm.py:126-135, gamma = -guidance_weight*sqrt(1-acp_t), v = -2 A^T r) and the
@@ -289,15 +314,43 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
 /* y = A(x) with a workspace of sp_op_workspace floats: sp_op_apply for the linear kinds (work
  * unused, may be NULL); PHASE: y = |FFT2(pad(x))| (sp_op_apply and sp_op_adjoint return
  * SP_EUNSUPPORTED for PHASE, as do sp_psld_pixel, sp_psld_cotangent and sp_pixel_opt_step);
- * PSF_FFT: y = A x, the extended correlation (the same entries return SP_EUNSUPPORTED for it). */
+ * PSF_FFT: y = A x, the extended correlation (the same entries return SP_EUNSUPPORTED for it);
+ * PSF_PERIODIC: y = A x = Re IFFT2(FFT2(x) * M), likewise. */
 int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
                    sp_stream_t stream);
 /* dx = J(x)^T g for the nonlinear kinds (g: batch rows of m, dx: batch rows of n).  PHASE:
  * crop(Re(IFFT2(g * z/|z|))) with z = FFT2(pad(x)) recomputed, z/|z| = 0 at |z| = 0 (never NaN
- * or inf).  PSF_FFT: dx = A^T g, the exact adjoint (x is not read).  SP_EUNSUPPORTED for the
+ * or inf).  PSF_FFT: dx = A^T g, the exact adjoint (x is not read); PSF_PERIODIC the same, with
+ * the multiplier conj(M).  SP_EUNSUPPORTED for the
  * linear kinds without a workspace, whose VJP is sp_op_adjoint. */
 int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
                  float* work, sp_stream_t stream);
+
+/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC); SP_EUNSUPPORTED for every other kind, SP_EINVAL
+ * for a rejected descriptor or argument first.  No reference counterpart: the reference's
+ * SVDOperator.apply_pseudo_inverse (linear.py) is the dense form of the same map.
+ *   sp_op_pinv_ws        x = A^+ y = Re IFFT2(FFT2(y) * P) (transpose = 0) or A^+T y (transpose =
+ *                        1, multiplier conj(P)): rows, columns, rows^-1 through `work`
+ *                        (sp_op_workspace floats), three launches.
+ *   sp_pgdm_prepare      q = P * FFT2(y) / (H W) for each of `rows` observation rows, as (re, im)
+ *                        pairs [row][channels][width/2 + 1][height] (the intermediate's layout);
+ *                        q is the caller's, 2 * rows * channels * (width/2 + 1) * height floats.
+ *                        Two launches.  Once per sampler call: y is fixed across its steps.
+ *   sp_pgdm_residual_ws  PGDM pass 1 (pgdm.py:104-119 up to the prior's VJP):
+ *                          x0 = (x - k*eps)/a,  v = grad_scale * (A^+ y - A^+ A x0) -> v_out
+ *                        which with grad_scale = -2 is the gradient of |A^+ y - A^+ A x0|^2 in
+ *                        x0 (A^+ A is an orthogonal projection).  Three launches: row FFTs of
+ *                        x0 -> work; per column tile the forward column FFT,
+ *                        z <- grad_scale * (q[b / y_div] - (P != 0 ? z / (H W) : 0)) and the inverse
+ *                        column FFT, in LDS; inverse row FFTs, real part -> v.  Sample b uses
+ *                        row b / y_div of q.  Pass 2 is sp_dps_update with rsq_partial = NULL.
+ * work and q must not alias any other argument. */
+int sp_op_pinv_ws(const sp_op* op, const float* y, float* x, int64_t batch, int32_t transpose,
+                  float* work, sp_stream_t stream);
+int sp_pgdm_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_stream_t stream);
+int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const float* q,
+                        int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
+                        float* work, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
  *   r = y[b/y_div] - z[b];  g[b] = grad_scale * r;  rsq_partial[b][p] += r^2 partials.

@@ -20,9 +20,12 @@ DEBUG_LIB_PATH = Path(__file__).resolve().parent / "lib" / "debug" / "libsampler
 SP_OP_IDENTITY, SP_OP_INPAINT, SP_OP_BLUR, SP_OP_MASK, SP_OP_SR, SP_OP_PSF = 0, 1, 2, 3, 4, 5
 SP_OP_PHASE = 6  # nonlinear: sp_op_apply_ws / sp_op_vjp_ws, no adjoint
 SP_OP_PSF_FFT = 7  # linear through a workspace: sp_op_apply_ws = A, sp_op_vjp_ws = A^T
+# periodic blur, diagonal in the H x W transform: the above plus sp_op_pinv_ws = A^+ / A^+T and the
+# fused PGDM pass 1 (sp_pgdm_prepare, sp_pgdm_residual_ws)
+SP_OP_PSF_PERIODIC = 8
 # sp_op_traits bits: what a kind does at the entry points (the library's table, not a list here)
 SP_TRAIT_UPDATE_READS_V, SP_TRAIT_DPS_WORKSPACE, SP_TRAIT_FUSED_LATENT = 1, 2, 4
-SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U = 8, 16
+SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U, SP_TRAIT_PINV = 8, 16, 32
 
 _ERRORS = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported"}
 
@@ -110,6 +113,9 @@ SIGNATURES = {
     "sp_op_traits": (ctypes.c_uint32, [_OPP]),
     "sp_op_apply_ws": (ctypes.c_int, [_OPP, _P, _P, _I64, _P, _P]),
     "sp_op_vjp_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _P, _P]),
+    "sp_op_pinv_ws": (ctypes.c_int, [_OPP, _P, _P, _I64, ctypes.c_int32, _P, _P]),
+    "sp_pgdm_prepare": (ctypes.c_int, [_OPP, _P, _I64, _P, _P]),
+    "sp_pgdm_residual_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _COP, _P, _P, _P]),
     "sp_residual_grad": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "sp_psld_pixel": (ctypes.c_int, [_OPP, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "sp_sum_partials": (ctypes.c_int, [_P, _I64, _P, _P]),

@@ -462,12 +462,18 @@ static const op_kind g_kinds[] = {
     {psf_fft_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace, psf_fft_dps_residual,
      nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr, nullptr, nullptr,
      SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
+    /* SP_OP_PSF_PERIODIC: PSF_FFT's launches on exact-size transforms (nothing extended or
+       folded), and the only kind with the pseudo-inverse columns: A^+, the PGDM pass 1 */
+    {psf_periodic_valid, psf_periodic_partials, psf_periodic_workspace, psf_periodic_workspace,
+     psf_periodic_dps_residual, nullptr, nullptr, psf_periodic_apply, psf_periodic_vjp, nullptr,
+     nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
+     psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual},
 };
 #undef SP_ELEMENTWISE_ROW
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
-                  kKinds == 8,
+                  SP_OP_PSF_PERIODIC == 8 && kKinds == 9,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -485,7 +491,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 106; }
+int sp_version(void) { return 107; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -762,6 +768,35 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
     const op_kind* k = kind_of(op);
     if (!k->adjoint) return SP_EUNSUPPORTED;  // nonlinear: sp_op_vjp_ws
     return k->adjoint(op, y, x, batch, static_cast<hipStream_t>(stream));
+}
+
+int sp_op_pinv_ws(const sp_op* op, const float* y, float* x, int64_t batch, int32_t transpose,
+                  float* work, sp_stream_t stream) {
+    if (!valid_op(op) || !y || !x || !work || batch <= 0 || batch > 65535 ||
+        (transpose != 0 && transpose != 1))
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->pinv_ws) return SP_EUNSUPPORTED;
+    return k->pinv_ws(op, y, x, batch, transpose, work, static_cast<hipStream_t>(stream));
+}
+
+int sp_pgdm_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_stream_t stream) {
+    if (!valid_op(op) || !y || !q || rows <= 0 || rows > 65535) return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->pgdm_prepare) return SP_EUNSUPPORTED;
+    return k->pgdm_prepare(op, y, rows, q, static_cast<hipStream_t>(stream));
+}
+
+int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const float* q,
+                        int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
+                        float* work, sp_stream_t stream) {
+    if (!valid_op(op) || !x || !eps || !q || !c || !v_out || !work || batch <= 0 || y_div <= 0 ||
+        batch > 65535)
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->pgdm_residual) return SP_EUNSUPPORTED;
+    return k->pgdm_residual(op, x, eps, q, batch, y_div, *c, v_out, work,
+                            static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

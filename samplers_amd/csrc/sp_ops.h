@@ -36,6 +36,12 @@ typedef int psld_cotangent_fn(const sp_op* op, const float* atr, const float* u,
 typedef int pixel_opt_fn(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq,
                          const float* y, int64_t batch, int64_t y_div, float gs,
                          const sp_adamw_coefs* c, const int32_t* stop, float* partial, hipStream_t s);
+typedef int pinv_ws_fn(const sp_op* op, const float* y, float* x, int64_t batch, int transpose,
+                       float* work, hipStream_t s);
+typedef int pgdm_prepare_fn(const sp_op* op, const float* y, int64_t rows, float* q, hipStream_t s);
+typedef int pgdm_residual_fn(const sp_op* op, const float* x, const float* eps, const float* q,
+                             int64_t batch, int64_t y_div, const sp_dps_coefs& c, float* v,
+                             float* work, hipStream_t s);
 
 // One row per sp_op kind.  A null member is the library's answer for a kind without that pass:
 // 0 floats of workspace, or SP_EUNSUPPORTED (apply_ws: sp_op_apply).
@@ -51,6 +57,11 @@ struct op_kind {
     psld_cotangent_fn* psld_cotangent;
     pixel_opt_fn* pixel_opt;
     uint32_t traits;  // SP_TRAIT_* (samplers_hip.h)
+    // the kinds with a pseudo-inverse of their own (SP_TRAIT_PINV): A^+ / A^+T through the
+    // workspace and the fused PGDM pass 1
+    pinv_ws_fn* pinv_ws;
+    pgdm_prepare_fn* pgdm_prepare;
+    pgdm_residual_fn* pgdm_residual;
 };
 
 const op_kind* kind_of(const sp_op* op);  // null for an unknown kind or a null op
@@ -58,15 +69,19 @@ bool valid_op(const sp_op* op);
 int64_t tiles_elementwise(int64_t n);
 
 // the kinds' functions, one line per column of the table (sp_blur.hip, sp_sr.hip, sp_psf.hip,
-// sp_phase.hip, sp_psf_fft.hip; elementwise_*: sp_latent.hip, the cotangent serves BLUR and PSF over A^T A u too)
-valid_fn blur_valid, sr_valid, psf_valid, phase_valid, psf_fft_valid;
-partials_fn blur_partials, sr_partials, psf_partials, phase_partials, psf_fft_partials;
-workspace_fn psf_workspace, phase_workspace, psf_fft_workspace;
+// sp_phase.hip, sp_psf_fft.hip with psf_periodic_* too; elementwise_*: sp_latent.hip, the cotangent serves BLUR and PSF over A^T A u too)
+valid_fn blur_valid, sr_valid, psf_valid, phase_valid, psf_fft_valid, psf_periodic_valid;
+partials_fn blur_partials, sr_partials, psf_partials, phase_partials, psf_fft_partials,
+    psf_periodic_partials;
+workspace_fn psf_workspace, phase_workspace, psf_fft_workspace, psf_periodic_workspace;
 dps_residual_fn blur_dps_residual, sr_dps_residual, psf_dps_residual, phase_dps_residual,
-    psf_fft_dps_residual;
+    psf_fft_dps_residual, psf_periodic_dps_residual;
 map_fn blur_apply, blur_adjoint, sr_apply, sr_adjoint, psf_apply, psf_adjoint;
-apply_ws_fn phase_apply, psf_fft_apply;
-vjp_ws_fn phase_vjp, psf_fft_vjp;
+apply_ws_fn phase_apply, psf_fft_apply, psf_periodic_apply;
+vjp_ws_fn phase_vjp, psf_fft_vjp, psf_periodic_vjp;
+pinv_ws_fn psf_periodic_pinv;
+pgdm_prepare_fn psf_periodic_pgdm_prepare;
+pgdm_residual_fn psf_periodic_pgdm_residual;
 psld_pixel_fn elementwise_psld_pixel, sr_psld_pixel;
 psld_cotangent_fn elementwise_psld_cotangent, sr_psld_cotangent;
 pixel_opt_fn elementwise_pixel_opt, sr_pixel_opt;

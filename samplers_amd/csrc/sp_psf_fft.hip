@@ -36,6 +36,10 @@
 // computed alone, lines are assigned by plane and tile only, the r^2 partial of a
 // (plane, row tile) is block_sum's fixed order: the bits do not depend on the batch, y_div or the
 // shard.  Plain stores, no atomics.
+//
+// SP_OP_PSF_PERIODIC (at the end of the file) runs the same kernels on exact-size transforms,
+// Nh = H and Nw = W, where the wrap-around blur is diagonal: nothing extended or folded, and a
+// pseudo-inverse that is one more multiplier.
 
 #include <algorithm>
 
@@ -47,6 +51,7 @@ namespace sp {
 
 enum { PF_REFLECT = 0, PF_CIRCULAR = 1, PF_ZEROS = 2 };
 enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2 };
+enum { PF_COL_MAP = 0, PF_COL_PREPARE = 1, PF_COL_PGDM = 2 };
 
 // smallest 2^k or 3 * 2^k in [8, 1024] that is >= n; 0 if there is none
 static int pf_size(int n) {
@@ -147,8 +152,17 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows(pf_geom g, const float* __re
 }
 
 // launch 2.  ADJ false: A (extend, conj(Hs), keep rows 0 .. H-1); true: A^T (Hs, fold).
-template <bool ADJ>
-__global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restrict__ ws, int T) {
+// EXT false: the periodic kind (SP_OP_PSF_PERIODIC, below) - Nh == H, nothing to extend or fold,
+// g.spec is the map's own multiplier (ADJ: its conjugate).  FORM (EXT false only):
+//   PF_COL_PREPARE  forward transform, times spec / (Nh Nw), stored as the spectrum it is
+//                   (sp_pgdm_prepare: Q = P * FFT2(y));
+//   PF_COL_PGDM     z <- gs (Q[b / y_div] - (spec != 0 ? z / (Nh Nw) : 0)) between the transforms
+//                   (sp_pgdm_residual_ws: spec = P, so spec != 0 is the kept set).
+template <bool ADJ, bool EXT = true, int FORM = PF_COL_MAP>
+__global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restrict__ ws, int T,
+                                                    const float2* __restrict__ qs, int64_t y_div,
+                                                    float gs) {
+    static_assert(EXT ? FORM == PF_COL_MAP : (FORM == PF_COL_MAP || !ADJ), "forms of the periodic kind");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int N = g.Nh, NP = phase_np(N);
     float2* tw = reinterpret_cast<float2*>(smem);
@@ -158,16 +172,16 @@ __global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restric
     const int c = static_cast<int>(blockIdx.x) / tiles;
     const int kw0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
     const int64_t plane = (int64_t)blockIdx.y * g.C + c;
-    SP_DCHECK(c < g.C && kw0 < g.HW);
+    SP_DCHECK(c < g.C && kw0 < g.HW && (EXT || N == g.H));
     float2* __restrict__ wp = ws + (plane * g.HW + kw0) * (int64_t)g.H;  // the tile's columns
     const int lines = min(T, g.HW - kw0);
-    const int ext = ADJ ? g.H : g.H + 2 * g.R;
+    const int ext = ADJ || !EXT ? g.H : g.H + 2 * g.R;
 
     phase_twiddles(tw, N);
     for (int t = 0; t < T; ++t)
         for (int q = threadIdx.x; q < N; q += kBlock) {
             float2 val = make_float2(0.f, 0.f);
-            const int h = q < ext ? (ADJ ? q : pf_src(q, g.R, g.H, g.mode)) : -1;
+            const int h = q < ext ? (ADJ || !EXT ? q : pf_src(q, g.R, g.H, g.mode)) : -1;
             if (t < lines && h >= 0) {
                 SP_DCHECK(h < g.H);
                 val = wp[t * g.H + h];
@@ -182,15 +196,36 @@ __global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restric
     const float s = 1.f / ((float)g.Nh * (float)g.Nw);
     const float2* __restrict__ hsp = g.spec + (int64_t)kw0 * N;
     const int total = lines * N;
-    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
-        const int t = idx / N, kh = idx - t * N;
-        SP_DCHECK(t < lines && kw0 + t < g.HW);
-        float2 hs = hsp[idx];
-        hs.x *= s;
-        hs.y *= ADJ ? s : -s;
-        float2* zp = z + t * NP + phase_slot(kh);
-        *zp = cmul(*zp, hs);
+    if constexpr (FORM == PF_COL_PGDM) {
+        const int64_t qplane = ((int64_t)blockIdx.y / y_div) * g.C + c;
+        const float2* __restrict__ qp = qs + (qplane * g.HW + kw0) * (int64_t)N;
+        for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int t = idx / N, kh = idx - t * N;
+            SP_DCHECK(t < lines && kw0 + t < g.HW && kh < g.H);
+            const float2 p = hsp[idx], qv = qp[idx];
+            float2* zp = z + t * NP + phase_slot(kh);
+            const bool kept = p.x != 0.f || p.y != 0.f;
+            const float2 pz = kept ? make_float2(s * zp->x, s * zp->y) : make_float2(0.f, 0.f);
+            *zp = make_float2(gs * (qv.x - pz.x), gs * (qv.y - pz.y));
+        }
+    } else {
+        constexpr bool CONJ = EXT ? !ADJ : ADJ;
+        for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int t = idx / N, kh = idx - t * N;
+            SP_DCHECK(t < lines && kw0 + t < g.HW);
+            float2 hs = hsp[idx];
+            hs.x *= s;
+            hs.y *= CONJ ? -s : s;
+            float2* zp = z + t * NP + phase_slot(kh);
+            if constexpr (FORM == PF_COL_PREPARE) {
+                SP_DCHECK(idx < lines * g.H);
+                wp[idx] = cmul(*zp, hs);  // N == H: the spectrum fills the columns it came from
+            } else {
+                *zp = cmul(*zp, hs);
+            }
+        }
     }
+    if constexpr (FORM == PF_COL_PREPARE) return;
     __syncthreads();
     const float2* u = phase_fft(z, z == A ? B : A, tw, N, NP, T, true);
     const int keep = lines * g.H;
@@ -198,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restric
         const int t = idx / g.H, h = idx - t * g.H;
         const float2* ul = u + t * NP;
         float2 val;
-        if constexpr (ADJ) {
+        if constexpr (ADJ && EXT) {
             int lo, hi;
             pf_images(h, g.R, g.H, g.mode, lo, hi);
             SP_DCHECK(g.R + h < N && lo < g.R && (hi < 0 || (hi >= g.H + g.R && hi < g.H + 2 * g.R)));
@@ -347,6 +382,7 @@ int64_t psf_fft_workspace(const sp_op* op, int64_t batch) {
 
 static const sp_step_rec* const kNoSched = nullptr;
 static const int32_t* const kNoCursor = nullptr;
+static const float2* const kNoSpec = nullptr;
 
 // rows, columns, rows^-1 of A (ADJ false) or A^T (true): in -> work -> out
 template <bool ADJ>
@@ -360,7 +396,7 @@ static int pf_map(const char* what, const sp_op* op, const float* in, float* out
     int rc = check_launch(what);
     if (rc != SP_OK) return rc;
     launch_w(0, 0.0, k_pf_cols<ADJ>, sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock),
-             phase_lds_bytes(g.Nh), s, g, ws, phase_lines(g.Nh));
+             phase_lds_bytes(g.Nh), s, g, ws, phase_lines(g.Nh), kNoSpec, (int64_t)1, 0.f);
     rc = check_launch(what);
     if (rc != SP_OK) return rc;
     launch_w(0, 0.0, k_pf_rows_inv<ADJ ? PF_OUT_AT : PF_OUT_A>, rows, dim3(kBlock),
@@ -395,18 +431,170 @@ int psf_fft_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_
              r.x, r.eps, r.a, r.k, ws, TR, r.sched, r.cursor);
     int rc = check_launch(what);
     if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false>, cols, dim3(kBlock), lc, s, g, ws, TC);
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false>, cols, dim3(kBlock), lc, s, g, ws, TC, kNoSpec,
+             (int64_t)1, 0.f);
     rc = check_launch(what);
     if (rc != SP_OK) return rc;
     launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, rows, dim3(kBlock), lr, s, g, ws,
              (float*)nullptr, r.y, r.y_div, r.gs, r.partial, P, TR, r.sched, r.cursor);
     rc = check_launch(what);
     if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<true>, cols, dim3(kBlock), lc, s, g, ws, TC);
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<true>, cols, dim3(kBlock), lc, s, g, ws, TC, kNoSpec,
+             (int64_t)1, 0.f);
     rc = check_launch(what);
     if (rc != SP_OK) return rc;
     launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_AT>, rows, dim3(kBlock), lr, s, g, ws, r.v,
              (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, TR, kNoSched, kNoCursor);
+    return check_launch(what);
+}
+
+// ---------------------------------------------------------------------------
+// SP_OP_PSF_PERIODIC: the wrap-around correlation on an image whose own sizes are transform
+// lengths (Nh = H, Nw = W).  The blur is then exactly diagonal in the transform the kernels
+// compute: A = IFFT2 M FFT2 with M = conj(FFT2(h centred at [0, 0])), so nothing is extended or
+// folded, A^T has the multiplier conj(M), and the pseudo-inverse truncated to the kept frequencies
+// has P = kept ? 1 / M : 0 (operators/periodic.py; both computed in fp64 by the caller).
+// op.taps = M then P, each (re, im) pairs [W / 2 + 1][H].  The launches are the ones above with
+// EXT = false: rows<., false>, cols<., false, .>, rows_inv<PF_OUT_A | PF_OUT_RESIDUAL>.
+// ---------------------------------------------------------------------------
+enum { PP_SPEC_M = 0, PP_SPEC_P = 1 };
+
+bool psf_periodic_valid(const sp_op* op) {  // radius = R, factor = 0, taps = M then P
+    if (!op->taps || op->keep_bits || op->word_rank || op->factor != 0 || op->channels <= 0 ||
+        !phase_size_ok(op->height) || !phase_size_ok(op->width) || op->radius < 1 ||
+        op->radius > (std::min(op->height, op->width) - 1) / 2)  // 2R + 1 <= min(H, W)
+        return false;
+    return (int64_t)op->channels * op->height * op->width == op->n && op->m == op->n;
+}
+
+static pf_geom pp_geometry(const sp_op* op, int which) {
+    pf_geom g;
+    g.C = op->channels, g.H = op->height, g.W = op->width, g.R = op->radius, g.mode = PF_CIRCULAR;
+    g.Nh = op->height, g.Nw = op->width;
+    g.HW = g.Nw / 2 + 1;
+    g.spec = reinterpret_cast<const float2*>(op->taps) + (int64_t)which * g.HW * g.Nh;
+    return g;
+}
+
+int64_t psf_periodic_partials(const sp_op* op) {
+    return (int64_t)op->channels * pf_row_tiles(pp_geometry(op, PP_SPEC_M));
+}
+
+int64_t psf_periodic_workspace(const sp_op* op, int64_t batch) {
+    const pf_geom g = pp_geometry(op, PP_SPEC_M);
+    return 2 * batch * g.C * (int64_t)g.HW * g.H;
+}
+
+// rows, columns, rows^-1 with the multiplier g.spec (CONJ: its conjugate): in -> work -> out
+template <bool CONJ>
+static int pp_map(const char* what, const pf_geom& g, const float* in, float* out, int64_t batch,
+                  float* work, hipStream_t s) {
+    float2* ws = reinterpret_cast<float2*>(work);
+    const dim3 rows = sample_grid(g.C * pf_row_tiles(g), batch);
+    launch_w(0, 0.0, k_pf_rows<false, false>, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, g, in,
+             (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), kNoSched, kNoCursor);
+    int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(0, 0.0, k_pf_cols<CONJ, false>, sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock),
+             phase_lds_bytes(g.Nh), s, g, ws, phase_lines(g.Nh), kNoSpec, (int64_t)1, 0.f);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(0, 0.0, k_pf_rows_inv<PF_OUT_A>, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, g, ws,
+             out, (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, phase_lines(g.Nw),
+             kNoSched, kNoCursor);
+    return check_launch(what);
+}
+
+int psf_periodic_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                       hipStream_t s) {
+    return pp_map<false>("sp_op_apply_ws", pp_geometry(op, PP_SPEC_M), x, y, batch, work, s);
+}
+
+int psf_periodic_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
+                     float* work, hipStream_t s) {
+    (void)x;
+    return pp_map<true>("sp_op_vjp_ws", pp_geometry(op, PP_SPEC_M), gy, dx, batch, work, s);
+}
+
+// A^+ (multiplier P) or its transpose (conj(P))
+int psf_periodic_pinv(const sp_op* op, const float* y, float* x, int64_t batch, int transpose,
+                      float* work, hipStream_t s) {
+    const pf_geom g = pp_geometry(op, PP_SPEC_P);
+    return transpose ? pp_map<true>("sp_op_pinv_ws", g, y, x, batch, work, s)
+                     : pp_map<false>("sp_op_pinv_ws", g, y, x, batch, work, s);
+}
+
+// the five launches of psf_fft_dps_residual on exact-size transforms
+int psf_periodic_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    const pf_geom g = pp_geometry(op, PP_SPEC_M);
+    float2* ws = reinterpret_cast<float2*>(r.work);
+    const int P = static_cast<int>(psf_periodic_partials(op));
+    const int TR = phase_lines(g.Nw), TC = phase_lines(g.Nh);
+    const size_t lr = phase_lds_bytes(g.Nw), lc = phase_lds_bytes(g.Nh);
+    const dim3 rows = sample_grid(P, r.batch), cols = sample_grid(g.C * pf_col_tiles(g), r.batch);
+    const char* what = "sp_dps_residual_ws";
+    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_pf_rows<true, false>, rows, dim3(kBlock), lr, s, g,
+             r.x, r.eps, r.a, r.k, ws, TR, r.sched, r.cursor);
+    int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false, false>, cols, dim3(kBlock), lc, s, g, ws, TC,
+             kNoSpec, (int64_t)1, 0.f);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, rows, dim3(kBlock), lr, s, g, ws,
+             (float*)nullptr, r.y, r.y_div, r.gs, r.partial, P, TR, r.sched, r.cursor);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<true, false>, cols, dim3(kBlock), lc, s, g, ws, TC,
+             kNoSpec, (int64_t)1, 0.f);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_A>, rows, dim3(kBlock), lr, s, g, ws, r.v,
+             (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, TR, kNoSched, kNoCursor);
+    return check_launch(what);
+}
+
+// Q = P * FFT2(y) / (H W) per observation row, in the intermediate's layout: rows, then the
+// column launch that stops at the spectrum.  y is fixed across a sampler call's steps, so this
+// runs once and every step's column launch reads Q instead of transforming y again.
+int psf_periodic_pgdm_prepare(const sp_op* op, const float* y, int64_t rows_y, float* q,
+                              hipStream_t s) {
+    const pf_geom g = pp_geometry(op, PP_SPEC_P);
+    float2* qs = reinterpret_cast<float2*>(q);
+    const char* what = "sp_pgdm_prepare";
+    launch_w(0, 0.0, k_pf_rows<false, false>, sample_grid(g.C * pf_row_tiles(g), rows_y),
+             dim3(kBlock), phase_lds_bytes(g.Nw), s, g, y, (const float*)nullptr, 1.f, 0.f, qs,
+             phase_lines(g.Nw), kNoSched, kNoCursor);
+    const int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(0, 0.0, k_pf_cols<false, false, PF_COL_PREPARE>,
+             sample_grid(g.C * pf_col_tiles(g), rows_y), dim3(kBlock), phase_lds_bytes(g.Nh), s, g,
+             qs, phase_lines(g.Nh), kNoSpec, (int64_t)1, 0.f);
+    return check_launch(what);
+}
+
+// v = gs (A^+ y - Pi x0): rows (x, eps -> work), columns (z <- gs (Q - kept z) between the
+// transforms), rows^-1 (work -> v)
+int psf_periodic_pgdm_residual(const sp_op* op, const float* x, const float* eps, const float* q,
+                               int64_t batch, int64_t y_div, const sp_dps_coefs& c, float* v,
+                               float* work, hipStream_t s) {
+    const pf_geom g = pp_geometry(op, PP_SPEC_P);
+    float2* ws = reinterpret_cast<float2*>(work);
+    const dim3 rows = sample_grid(g.C * pf_row_tiles(g), batch);
+    const char* what = "sp_pgdm_residual_ws";
+    launch_w(TK_DPS_RESIDUAL, (double)batch, k_pf_rows<true, false>, rows, dim3(kBlock),
+             phase_lds_bytes(g.Nw), s, g, x, eps, c.a, c.k, ws, phase_lines(g.Nw), kNoSched,
+             kNoCursor);
+    int rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false, false, PF_COL_PGDM>,
+             sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock), phase_lds_bytes(g.Nh), s, g,
+             ws, phase_lines(g.Nh), reinterpret_cast<const float2*>(q), y_div, c.grad_scale);
+    rc = check_launch(what);
+    if (rc != SP_OK) return rc;
+    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_A>, rows, dim3(kBlock),
+             phase_lds_bytes(g.Nw), s, g, ws, v, (const float*)nullptr, (int64_t)1, 0.f,
+             (float*)nullptr, 0, phase_lines(g.Nw), kNoSched, kNoCursor);
     return check_launch(what);
 }
 

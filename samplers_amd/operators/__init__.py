@@ -14,6 +14,7 @@ from .inpainting import (
 from .phase import PhaseRetrievalOperator
 from .linear import GeneralSVDOperator, LinearOperator, SVDOperator
 from .psf import MotionBlurOperator, PSFBlurOperator, motion_blur_kernel
+from .periodic import PeriodicBlurOperator, pseudo_inverse_spectrum, transfer_function
 from .psf_fft import FFTPSFBlurOperator, padded_size, psf_spectrum
 from .superres import SuperResolutionOperator
 
@@ -34,10 +35,13 @@ __all__ = [
     "PSFBlurOperator",
     "MotionBlurOperator",
     "FFTPSFBlurOperator",
+    "PeriodicBlurOperator",
     "PhaseRetrievalOperator",
     "motion_blur_kernel",
     "padded_size",
     "psf_spectrum",
+    "transfer_function",
+    "pseudo_inverse_spectrum",
     "get_mask_inpaint_center",
     "get_mask_side_painting",
     "get_mask_random",

@@ -15,7 +15,9 @@ The reference ships no blur operator, so the semantics are defined here and pinn
 * ``1 ≤ R ≤ min(H, W) − 1`` and ``H + 2R, W + 2R ≤ 1024`` (``padded_size``): every pixel then
   has at most three fold pre-images per axis;
 * the taps are used as given (any finite fp32 values, negative ones allowed, no normalisation);
-* no pseudo-inverse: ``PGDMSampler`` rejects the operator as it rejects ``PSFBlurOperator``.
+* no pseudo-inverse: ``PGDMSampler`` rejects the operator as it rejects ``PSFBlurOperator``
+  (``PeriodicBlurOperator`` in ``periodic.py`` is the circular map on an image whose own sizes are
+  transform lengths, where the blur is diagonal and has a spectral pseudo-inverse).
 
 On device tensors the maps run the ``SP_OP_PSF_FFT`` kernels (``csrc/sp_psf_fft.hip``: in-LDS row
 and column FFTs of ``Nh × Nw`` points, a multiply with the PSF's spectrum, the boundary handled by

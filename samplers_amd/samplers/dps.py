@@ -131,7 +131,7 @@ class FusedDPSStep:
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
                 "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses), "
-                "FFTPSFBlurOperator and PhaseRetrievalOperator"
+                "FFTPSFBlurOperator, PeriodicBlurOperator and PhaseRetrievalOperator"
             )
         _hip.require_cuda(observation_rows, "DPSSampler")
         if observation_rows.dtype != torch.float32:
@@ -150,13 +150,15 @@ class FusedDPSStep:
         if mode not in ("dps", "pgdm"):
             raise ValueError(mode)
         self.traits = int(self.lib.sp_op_traits(desc))
-        if mode == "pgdm" and not self.traits & _hip.SP_TRAIT_LINEAR:
+        self.pinv = bool(self.traits & _hip.SP_TRAIT_PINV)
+        if mode == "pgdm" and not self.traits & (_hip.SP_TRAIT_LINEAR | _hip.SP_TRAIT_PINV):
             raise NotImplementedError(f"{type(op).__name__} has no apply_pseudo_inverse (nonlinear, "
                                       "or a blur through a workspace): PGDM does not apply")
         self.mode = mode
         # DPS: d log p/d(Ax) = c r.  PGDM: d/dx0 of ||A^+ y - A^+ A x0||^2 = -c A^T r with the
         # operator's pinv_grad_scale c: 2 for the partial isometries (A^+ = A^T: identity,
-        # inpainting, mask), 2 s^2 for x s super-resolution (A^+ = s^2 A^T).
+        # inpainting, mask), 2 s^2 for x s super-resolution (A^+ = s^2 A^T).  A kind with a
+        # pseudo-inverse of its own (SP_TRAIT_PINV): v = -2 (A^+ y - A^+ A x0) from sp_pgdm_residual_ws.
         self.grad_scale = -float(getattr(op, "pinv_grad_scale", 2.0))
         if mode == "dps":
             gs = getattr(inverse_problem.noise, "grad_scale", None)
@@ -178,6 +180,16 @@ class FusedDPSStep:
         self.needs_v = bool(self.traits & _hip.SP_TRAIT_UPDATE_READS_V) or bool(reuse_v)
         self.micro_batch = micro_batch
         self.timer = timer
+        # PGDM through the kind's own pseudo-inverse: Q = P FFT2(y), once (y is fixed across steps)
+        self.q = None
+        if mode == "pgdm" and self.pinv:
+            rows = self.y.shape[0]
+            floats = int(self.lib.sp_op_workspace(desc, rows))
+            if floats <= 0:
+                raise _hip.HipLibraryError(f"sp_op_workspace rejected the descriptor ({floats})")
+            self.q = torch.empty((rows, floats // rows), device=self.y.device, dtype=torch.float32)
+            _hip.check(self.lib.sp_pgdm_prepare(desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
+                                                _hip.stream_of(self.y)), "sp_pgdm_prepare")
 
     def coefficients(self, t: int, t_prev: int, s: int) -> _hip.SpDpsCoefs:
         acp = host_alphas_cumprod(self.network)
@@ -228,10 +240,16 @@ class FusedDPSStep:
             if span:
                 span.__enter__()
             work = self.workspace(bc, xc)
-            _hip.check(lib.sp_dps_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc), bc,
-                                              self.y_div, coefs, _hip.ptr(v), _hip.ptr(part),
-                                              _hip.ptr(work), stream),
-                       "sp_dps_residual_ws")
+            if self.q is not None:
+                _hip.check(lib.sp_pgdm_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c),
+                                                   _hip.ptr(self.q[b0 // self.y_div:]), bc,
+                                                   self.y_div, coefs, _hip.ptr(v), _hip.ptr(work),
+                                                   stream), "sp_pgdm_residual_ws")
+            else:
+                _hip.check(lib.sp_dps_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc),
+                                                  bc, self.y_div, coefs, _hip.ptr(v), _hip.ptr(part),
+                                                  _hip.ptr(work), stream),
+                           "sp_dps_residual_ws")
             if span:
                 span.__exit__(None, None, None)
             (w,) = torch.autograd.grad(eps, xr, grad_outputs=v.view_as(eps))
