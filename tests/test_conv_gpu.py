@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from exact_cases import WINO_EMU_L2
 from samplers_amd import _hip
 from samplers_amd.networks.layers import Conv3x3
 
@@ -120,11 +121,16 @@ def test_conv3x3_timing_records_flops(cuda, monkeypatch):
                                    (2, 24, 64, 8, 32), (2, 32, 64, 16, 64), (1, 48, 64, 8, 32)])
 def test_winograd_forward_and_input_vjp(cuda, shape):
     """Winograd F(2x2,3x3) tile: fp32 transforms + exact fp32 MFMA accumulation; the
-    transforms add F(2,3) rounding, so the bound is 1e-5 relative L2 (vs 2e-6 direct).
+    transforms add F(2,3) rounding.  Bound: twice the relative L2 of the fp32 emulation of the same
+    algebra on the same operands (tests/exact_cases.py WINO_EMU_L2: 1.4e-7 - 7.1e-7 per shape; the
+    bound was 1e-5 before, 25-40x what the tile shows).
     W = 16 shapes run the 4 x 8-tile wave geometry (the UNet's 16x16 level); 8x8 shapes the
     same geometry over two images side by side (batches not a multiple of 4 included).
-    cin = 24 / 48 (not a multiple of twice the ξ-split tile's ring): the W % 32 layers' other
-    kernel; cin = 32: the ξ-split tile's shortest K (its first and last ring blocks only)."""
+    These raw calls pass no workspace, so nothing here splits K: with SP_WINO_DX = 3 and
+    SP_WINO_DU = 2 the ξ-split tile's ring has XI_NR = 4 slots and wino_xi()'s rule (cin % 8 == 0,
+    cin >= 16) is sp_wino3x3_supported's own, so every W % 32 and W = 16 shape runs k_wino3x3_xi
+    (cin = 24 / 48 included: an odd number of 8-channel ring blocks) and only the 8x8 mosaic runs
+    k_wino3x3_r; the unsplit k_wino3x3_r<., 16> / <., 8> are not reached by any launch."""
     n, cin, cout, h, w = shape
     lib = _hip.load_library()
     assert lib.sp_wino3x3_supported(cin, cout, h, w)
@@ -150,9 +156,9 @@ def test_winograd_forward_and_input_vjp(cuda, shape):
         _hip.check(lib.sp_wino3x3_bwd_input(dyg.data_ptr(), uv.data_ptr(), n, cin, cout, h, w,
                                             dx.data_ptr(), st), "wino bwd")
         rel = ((dx.double().cpu() - gref).norm() / gref.norm()).item()
-        assert rel < 1e-5, rel
+        assert rel < 2 * WINO_EMU_L2["raw"][shape][1], rel
     rel = ((y.double().cpu() - ref.detach()).norm() / ref.detach().norm()).item()
-    assert rel < 1e-5, rel
+    assert rel < 2 * WINO_EMU_L2["raw"][shape][0], rel
 
 
 @pytest.mark.parametrize("shape", [(1, 128, 128, 128, 128), (1, 256, 256, 64, 64), (1, 512, 512, 32, 32),
@@ -203,11 +209,12 @@ def test_winograd_split_k_workspace(cuda, shape):
 
     y1, y2, y0 = fwd(ws_f), fwd(ws_f), fwd(0)
     assert torch.equal(y1, y2)
-    assert ((y1.double().cpu() - ref).norm() / ref.norm()).item() < 1e-5
+    emu_f, emu_v = WINO_EMU_L2["split"][shape]
+    assert ((y1.double().cpu() - ref).norm() / ref.norm()).item() < 2 * emu_f
     assert ((y1 - y0).norm() / y0.norm()).item() < 1e-6
     d1, d2, d0 = vjp(ws_b), vjp(ws_b), vjp(0)
     assert torch.equal(d1, d2)
-    assert ((d1.double().cpu() - gref).norm() / gref.norm()).item() < 1e-5
+    assert ((d1.double().cpu() - gref).norm() / gref.norm()).item() < 2 * emu_v
     assert ((d1 - d0).norm() / d0.norm()).item() < 1e-6
 
 
