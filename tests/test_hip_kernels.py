@@ -270,9 +270,15 @@ def test_dispatch_packet_timing(cuda):
 
 
 @pytest.mark.parametrize("shape,ks,batch,ydiv,asym", [
-    ((3, 32, 256), 9, 2, 1, False), ((2, 64, 256), 9, 3, 3, False), ((1, 96, 256), 5, 2, 1, False),
-    ((3, 32, 256), 3, 1, 1, False), ((1, 64, 256), 7, 2, 2, False), ((3, 256, 256), 9, 2, 1, False),
-    ((2, 96, 256), 9, 2, 1, True), ((1, 64, 256), 5, 1, 1, True)])
+    ((3, 32, 256), 9, 2, 1, False),   # H / 32 = 1, odd: k_blur_dps_dma<4>
+    ((2, 64, 256), 9, 3, 3, False),   # H / 32 = 2, even: k_blur_dps_reg<4>
+    ((1, 96, 256), 5, 2, 1, False),   # H / 32 = 3, odd: k_blur_dps_dma<2>
+    ((3, 32, 256), 3, 1, 1, False),   # H / 32 = 1, odd: k_blur_dps_dma<1>
+    ((1, 64, 256), 7, 2, 2, False),   # H / 32 = 2, even: k_blur_dps_reg<3>
+    ((3, 256, 256), 9, 2, 1, False),  # H / 32 = 8, even: k_blur_dps_reg<4>
+    ((2, 96, 256), 9, 2, 1, True),    # H / 32 = 3, odd: k_blur_dps_dma<4>
+    ((1, 64, 256), 5, 1, 1, True)])   # H / 32 = 2, even: k_blur_dps_reg<2>
+# (k_blur_dps_reg<1> and k_blur_dps_dma<3> run in tests/test_blur_edges_gpu.py)
 def test_blur_streaming_residual_pass(cuda, shape, ks, batch, ydiv, asym):
     """The streaming blur pass (256-column planes, one wave per row segment, odd segments
     swept bottom-up) against the closed form with the fold-corrected reflect adjoint: every
