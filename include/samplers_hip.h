@@ -82,7 +82,7 @@ enum {
                            holds the PSF's SPECTRUM (below).  Linear, m == n, no
                            pseudo-inverse; the maps need a workspace:
                            sp_op_apply_ws = A, sp_op_vjp_ws = A^T (x not read)   */
-    SP_OP_PSF_PERIODIC = 8 /* new: the wrap-around correlation of a (2*radius+1)^2 PSF on
+    SP_OP_PSF_PERIODIC = 8, /* new: the wrap-around correlation of a (2*radius+1)^2 PSF on
                            an image whose own sizes are transform lengths: height and
                            width each 2^k or 3*2^k in [8, 1024], radius >= 1,
                            2*radius+1 <= min(height, width), factor = 0.  The map is
@@ -91,6 +91,14 @@ enum {
                            Linear, m == n; sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
                            sp_op_pinv_ws = A^+ / A^+T, sp_pgdm_prepare and
                            sp_pgdm_residual_ws the fused PGDM pass 1             */
+    SP_OP_RADON = 9     /* new: parallel-beam CT projector (Joseph's method, unit pixel
+                           and detector spacing), depthwise over channel planes:
+                           y is (channels, radius, factor) = (C, angles, detector
+                           bins), m = channels*radius*factor != n in general;
+                           8 <= height, width <= 512, 1 <= radius <= 512 angles,
+                           1 <= factor <= 1024 bins; taps holds one row per angle
+                           (below).  Linear, adjoint = exact transpose (a gather per
+                           pixel, no atomics); no pseudo-inverse                */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -122,17 +130,35 @@ typedef struct sp_op {
                                         P = 1/M on the kept frequencies and 0 on the
                                         others, the multiplier of A^+.  P must be
                                         conjugate-symmetric under k -> -k like M (a
-                                        symmetric kept set)                      */
+                                        symmetric kept set).  RADON: 4*radius floats,
+                                        one row (alpha, beta, length, axis) per angle
+                                        theta: axis 0 (|cos| >= |sin|): (1/cos,
+                                        -sin/cos, 1/|cos|, 0), ray s crosses image row
+                                        i at column alpha*(s - (factor-1)/2) +
+                                        (beta*(i - (height-1)/2) + (width-1)/2); axis
+                                        1: (1/sin, -cos/sin, 1/|sin|, 1), rows and
+                                        columns swapped.  y[a][s] = length * the sum
+                                        over the rows (columns) of the image linearly
+                                        interpolated at the crossing, 0 off the image.
+                                        The map is defined by these fp32 values taken
+                                        as exact; the library does not read them on
+                                        the host.  Preconditions: |alpha| >= 1,
+                                        |beta| <= 1, length finite, axis 0 or 1 (other
+                                        values stay in bounds, the result is then
+                                        unspecified)                             */
     int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
                                         zero rows added above and below.  PSF_FFT:
                                         1..min(height, width) - 1.  PSF_PERIODIC:
-                                        1..(min(height, width) - 1) / 2          */
+                                        1..(min(height, width) - 1) / 2.  RADON: the
+                                        number of angles, 1..512                 */
     int32_t factor;                  /* SR: 2, 4 or 8.  PHASE: pad_w >= 0, zero
                                         columns added left and right.  PSF_FFT: the
                                         boundary: 0 reflect, 1 circular, 2 zeros (0
-                                        for the other kinds).  PHASE: keep_bits,
+                                        for the other kinds).  RADON: the number of
+                                        detector bins, 1..1024.  PHASE: keep_bits,
                                         word_rank and taps must be NULL; PSF_FFT
-                                        and PSF_PERIODIC: keep_bits and word_rank */
+                                        and PSF_PERIODIC: keep_bits and word_rank;
+                                        RADON: keep_bits and word_rank too       */
 } sp_op;
 
 /* Scalars of one DPS step (all fp32, computed on the host exactly as the
@@ -217,13 +243,17 @@ int sp_debug_selftest(sp_stream_t stream);
  * m == n == channels*height*width and keep_bits and word_rank are NULL.  PSF_PERIODIC: the same
  * count with Nw = width; rejected unless taps != NULL, factor == 0, height and width are each 2^k
  * or 3*2^k in [8, 1024], radius >= 1, 2*radius + 1 <= min(height, width),
- * m == n == channels*height*width and keep_bits and word_rank are NULL. */
+ * m == n == channels*height*width and keep_bits and word_rank are NULL.  RADON: the workgroups
+ * per sample of its project launch, channels * radius * ceil(factor / 256) (csrc/sp_radon.hip);
+ * rejected unless taps != NULL, 1 <= radius <= 512, 1 <= factor <= 1024, 8 <= height, width <= 512,
+ * n == channels*height*width, m == channels*radius*factor and keep_bits and word_rank are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
 /* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
- * 0 for every kind but PSF (one pass, no workspace), batch * m for PSF (its residual launch
+ * 0 for every kind but those below (one pass, no workspace), batch * m for PSF (its residual launch
  * leaves grad_scale * r there for the adjoint launch), 2 * batch * channels * Nw * height for
  * PHASE (the complex row transforms, stored transposed), 2 * batch * channels * (Nw/2 + 1) * height
- * for PSF_FFT (the same, half the spectrum: the rows are real) and for PSF_PERIODIC (Nw = width).  SP_EINVAL for a rejected
+ * for PSF_FFT (the same, half the spectrum: the rows are real) and for PSF_PERIODIC (Nw = width),
+ * batch * m for RADON (grad_scale * r in sinogram space, between project and backproject).  SP_EINVAL for a rejected
  * descriptor or batch <= 0.  The library allocates nothing. */
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
 /* Floats of `work` that sp_op_apply_ws / sp_op_vjp_ws need: 0 for the linear kinds, the figure
@@ -267,7 +297,11 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  * per row tile the inverse row FFT, g = grad_scale * (y - A x0), one r^2 partial and the forward
  * row FFT of g; the column launch again with the spectrum and the fold; inverse row FFTs and the
  * fold -> v = A^T g.  PSF_PERIODIC: the same five launches on exact-size transforms (Nh = height,
- * Nw = width), nothing extended or folded.
+ * Nw = width), nothing extended or folded.  RADON runs here only too, as two launches
+ * (csrc/sp_radon.hip): `project` forms x0 while it stages its slab of the plane, sums every ray in
+ * row (column) order, writes work = grad_scale * (y - A x0) and one |r|^2 partial per workgroup;
+ * `backproject` gathers v = A^T work per pixel, angles in order.  The result has the same bits on
+ * every run and for a sample in any batch.
  * work must not alias any other argument. */
 int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const float* y,
                        int64_t batch, int64_t y_div, const sp_dps_coefs* c,
@@ -278,7 +312,7 @@ int sp_dps_residual_ws(const sp_op* op, const float* x, const float* eps, const 
  *   g   = v/a - (k/a) * w          (w = J_eps^T v from the prior's VJP)
  *   x'  = c_ell*x + c_s*x0 + std*xi + gamma/(sqrt(sum_p rsq_partial[b][p]) + norm_eps) * g
  * v: pass NULL to recompute v from (x, eps, y) (IDENTITY/INPAINT/MASK), else
- *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF, PHASE, PSF_FFT and PSF_PERIODIC, which run the
+ *    the buffer written by sp_dps_residual (required for BLUR, SR, PSF, PHASE, PSF_FFT, PSF_PERIODIC and RADON, which run the
  *    identity-kind update over it: the Philox element index stays the flat element index).
  * rsq_partial: NULL selects a fixed factor, x' = ... + gamma * g — the PGDM update
  *    (pgdm.py:126-135, gamma = -guidance_weight*sqrt(1-acp_t), v = -2 A^T r) and the
@@ -305,11 +339,14 @@ int sp_randn(float* out, int64_t batch, int64_t n, uint64_t seed, int64_t step,
 /* y = A x (operators/base.py:91-92; linear.py:141-152; inpainting.py:132-145).  SR: the block
  * means, each block summed in the fixed order documented in csrc/sp_sr.hip.  PSF: the
  * reflect-padded correlation, every pixel summed tap row by tap row over the rows' non-zero
- * spans (csrc/sp_psf.hip). */
+ * spans (csrc/sp_psf.hip).  RADON: the line integrals, every ray summed in row (column) order
+ * (csrc/sp_radon.hip). */
 int sp_op_apply(const sp_op* op, const float* x, float* y, int64_t batch, sp_stream_t stream);
 /* x = A^T y (linear.py:154-165; inpainting.py:169-187).  SR: y / factor^2 replicated over
  * each block (exact); the pseudo-inverse is factor^2 times this.  PSF: a gather (no atomics):
- * the zero-extended correlation plus the fold terms of the reflect padding, in a fixed order. */
+ * the zero-extended correlation plus the fold terms of the reflect padding, in a fixed order.
+ * RADON: a gather per pixel over the <= 2 rays per angle that touch it, with the weights of
+ * sp_op_apply bit for bit, angles in order. */
 int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_stream_t stream);
 /* y = A(x) with a workspace of sp_op_workspace floats: sp_op_apply for the linear kinds (work
  * unused, may be NULL); PHASE: y = |FFT2(pad(x))| (sp_op_apply and sp_op_adjoint return

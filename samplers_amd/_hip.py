@@ -23,6 +23,9 @@ SP_OP_PSF_FFT = 7  # linear through a workspace: sp_op_apply_ws = A, sp_op_vjp_w
 # periodic blur, diagonal in the H x W transform: the above plus sp_op_pinv_ws = A^+ / A^+T and the
 # fused PGDM pass 1 (sp_pgdm_prepare, sp_pgdm_residual_ws)
 SP_OP_PSF_PERIODIC = 8
+# parallel-beam CT projector (Joseph): linear, y of its own geometry (C, radius, factor), pass 1
+# in the _ws forms
+SP_OP_RADON = 9
 # sp_op_traits bits: what a kind does at the entry points (the library's table, not a list here)
 SP_TRAIT_UPDATE_READS_V, SP_TRAIT_DPS_WORKSPACE, SP_TRAIT_FUSED_LATENT = 1, 2, 4
 SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U, SP_TRAIT_PINV = 8, 16, 32

@@ -468,12 +468,17 @@ static const op_kind g_kinds[] = {
      psf_periodic_dps_residual, nullptr, nullptr, psf_periodic_apply, psf_periodic_vjp, nullptr,
      nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
      psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual},
+    /* SP_OP_RADON: as PSF (project, then backproject through the caller's work buffer), with an
+       observation space of its own geometry: m = channels * radius * factor */
+    {radon_valid, radon_partials, radon_workspace, nullptr, radon_dps_residual, radon_apply,
+     radon_adjoint, nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
 };
 #undef SP_ELEMENTWISE_ROW
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
-                  SP_OP_PSF_PERIODIC == 8 && kKinds == 9,
+                  SP_OP_PSF_PERIODIC == 8 && SP_OP_RADON == 9 && kKinds == 10,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -491,7 +496,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 107; }
+int sp_version(void) { return 108; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 

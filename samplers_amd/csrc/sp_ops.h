@@ -69,14 +69,17 @@ bool valid_op(const sp_op* op);
 int64_t tiles_elementwise(int64_t n);
 
 // the kinds' functions, one line per column of the table (sp_blur.hip, sp_sr.hip, sp_psf.hip,
-// sp_phase.hip, sp_psf_fft.hip with psf_periodic_* too; elementwise_*: sp_latent.hip, the cotangent serves BLUR and PSF over A^T A u too)
-valid_fn blur_valid, sr_valid, psf_valid, phase_valid, psf_fft_valid, psf_periodic_valid;
+// sp_phase.hip, sp_psf_fft.hip with psf_periodic_* too, sp_radon.hip; elementwise_*: sp_latent.hip, the cotangent serves BLUR, PSF
+// and RADON over A^T A u too)
+valid_fn blur_valid, sr_valid, psf_valid, phase_valid, psf_fft_valid, psf_periodic_valid, radon_valid;
 partials_fn blur_partials, sr_partials, psf_partials, phase_partials, psf_fft_partials,
-    psf_periodic_partials;
-workspace_fn psf_workspace, phase_workspace, psf_fft_workspace, psf_periodic_workspace;
+    psf_periodic_partials, radon_partials;
+workspace_fn psf_workspace, phase_workspace, psf_fft_workspace, psf_periodic_workspace,
+    radon_workspace;
 dps_residual_fn blur_dps_residual, sr_dps_residual, psf_dps_residual, phase_dps_residual,
-    psf_fft_dps_residual, psf_periodic_dps_residual;
-map_fn blur_apply, blur_adjoint, sr_apply, sr_adjoint, psf_apply, psf_adjoint;
+    psf_fft_dps_residual, psf_periodic_dps_residual, radon_dps_residual;
+map_fn blur_apply, blur_adjoint, sr_apply, sr_adjoint, psf_apply, psf_adjoint, radon_apply,
+    radon_adjoint;
 apply_ws_fn phase_apply, psf_fft_apply, psf_periodic_apply;
 vjp_ws_fn phase_vjp, psf_fft_vjp, psf_periodic_vjp;
 pinv_ws_fn psf_periodic_pinv;

@@ -16,6 +16,7 @@ from .linear import GeneralSVDOperator, LinearOperator, SVDOperator
 from .psf import MotionBlurOperator, PSFBlurOperator, motion_blur_kernel
 from .periodic import PeriodicBlurOperator, pseudo_inverse_spectrum, transfer_function
 from .psf_fft import FFTPSFBlurOperator, padded_size, psf_spectrum
+from .radon import RadonOperator, radon_table
 from .superres import SuperResolutionOperator
 
 __all__ = [
@@ -37,6 +38,8 @@ __all__ = [
     "FFTPSFBlurOperator",
     "PeriodicBlurOperator",
     "PhaseRetrievalOperator",
+    "RadonOperator",
+    "radon_table",
     "motion_blur_kernel",
     "padded_size",
     "psf_spectrum",
