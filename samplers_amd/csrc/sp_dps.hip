@@ -462,10 +462,10 @@ static const op_kind g_kinds[] = {
     {psf_fft_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace, psf_fft_dps_residual,
      nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr, nullptr, nullptr,
      SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
-    /* SP_OP_PSF_PERIODIC: PSF_FFT's launches on exact-size transforms (nothing extended or
+    /* SP_OP_PSF_PERIODIC: PSF_FFT's functions on exact-size transforms (nothing extended or
        folded), and the only kind with the pseudo-inverse columns: A^+, the PGDM pass 1 */
-    {psf_periodic_valid, psf_periodic_partials, psf_periodic_workspace, psf_periodic_workspace,
-     psf_periodic_dps_residual, nullptr, nullptr, psf_periodic_apply, psf_periodic_vjp, nullptr,
+    {psf_periodic_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace,
+     psf_fft_dps_residual, nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr,
      nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
      psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual},
     /* SP_OP_RADON: as PSF (project, then backproject through the caller's work buffer), with an

@@ -1,6 +1,6 @@
 // In-LDS Stockham FFT core shared by the kinds that transform in LDS (sp_phase.hip,
-// sp_psf_fft.hip; the algorithm and the LDS layout are described in sp_phase.hip's file comment).
-// Internal; include after sp_ops.h, inside a translation unit that defines SP_TU.
+// sp_psf_fft.hip; the algorithm and the LDS layout are described in sp_phase.hip's file comment),
+// and at the end the one host helper, fft_stage, through which those kinds launch.  Internal; include after sp_ops.h, inside a translation unit that defines SP_TU.
 #pragma once
 
 #include "sp_ops.h"
@@ -128,6 +128,26 @@ __device__ __forceinline__ float2* phase_fft(float2* a, float2* b, const float2*
         a = b;
     }
     return a;
+}
+
+// ---------------------------------------------------------------------------
+// host side: how every kind launches a stage of N-point transforms
+// ---------------------------------------------------------------------------
+// typed nulls for the kernel arguments a stage does not use
+constexpr const float* kNoIn = nullptr;
+constexpr float* kNoOut = nullptr;
+constexpr const sp_step_rec* kNoSched = nullptr;
+constexpr const int32_t* kNoCursor = nullptr;
+
+// `gx` workgroups per sample of `kernel` on N-point transforms (phase_lds_bytes(N) of dynamic
+// LDS), reported under the entry point `what`; kind / work as launch_w (kind 0: untimed); the
+// kernel's own arguments follow, phase_lines(N) among them
+template <typename K, typename... Args>
+static inline int fft_stage(const char* what, int kind, double work, K kernel, int64_t gx,
+                            int64_t batch, int N, hipStream_t s, Args... args) {
+    launch_w(kind, work, kernel, sample_grid(gx, batch), dim3(kBlock), (size_t)phase_lds_bytes(N), s,
+             args...);
+    return check_launch(what);
 }
 
 }  // namespace sp

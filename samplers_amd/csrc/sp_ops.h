@@ -1,8 +1,9 @@
 // Per-kind dispatch of the operator entry points (internal; includes sp_common.h).  Every
 // `extern "C"` entry that takes an sp_op checks its common arguments, looks the kind's row up and
 // calls through it.  The rows are filled in sp_dps.hip; a kind's functions live in its own file
-// (IDENTITY / INPAINT / MASK share one set, next to their kernels in sp_dps.hip and sp_latent.hip)
-// and are called with a descriptor that passed valid_op() and the entry's arguments checked.
+// (IDENTITY / INPAINT / MASK share one set, next to their kernels in sp_dps.hip and sp_latent.hip;
+// PSF_FFT / PSF_PERIODIC share the maps and DPS pass 1 of sp_psf_fft.hip; the kinds that transform
+// in LDS launch every stage through fft_stage of sp_fft.h) and are called with a descriptor that passed valid_op() and the entry's arguments checked.
 #pragma once
 
 #include "sp_common.h"
@@ -69,19 +70,20 @@ bool valid_op(const sp_op* op);
 int64_t tiles_elementwise(int64_t n);
 
 // the kinds' functions, one line per column of the table (sp_blur.hip, sp_sr.hip, sp_psf.hip,
-// sp_phase.hip, sp_psf_fft.hip with psf_periodic_* too, sp_radon.hip; elementwise_*: sp_latent.hip, the cotangent serves BLUR, PSF
-// and RADON over A^T A u too)
+// sp_phase.hip, sp_psf_fft.hip, sp_radon.hip; elementwise_*: sp_latent.hip, the cotangent serves
+// BLUR, PSF and RADON over A^T A u too).  sp_psf_fft.hip holds two kinds on one pipeline: the
+// psf_fft_* functions serve PSF_FFT and PSF_PERIODIC alike (they branch on op->kind where the
+// geometry differs); psf_periodic_* are the periodic kind's own rules and pseudo-inverse passes.
 valid_fn blur_valid, sr_valid, psf_valid, phase_valid, psf_fft_valid, psf_periodic_valid, radon_valid;
 partials_fn blur_partials, sr_partials, psf_partials, phase_partials, psf_fft_partials,
-    psf_periodic_partials, radon_partials;
-workspace_fn psf_workspace, phase_workspace, psf_fft_workspace, psf_periodic_workspace,
-    radon_workspace;
+    radon_partials;
+workspace_fn psf_workspace, phase_workspace, psf_fft_workspace, radon_workspace;
 dps_residual_fn blur_dps_residual, sr_dps_residual, psf_dps_residual, phase_dps_residual,
-    psf_fft_dps_residual, psf_periodic_dps_residual, radon_dps_residual;
+    psf_fft_dps_residual, radon_dps_residual;
 map_fn blur_apply, blur_adjoint, sr_apply, sr_adjoint, psf_apply, psf_adjoint, radon_apply,
     radon_adjoint;
-apply_ws_fn phase_apply, psf_fft_apply, psf_periodic_apply;
-vjp_ws_fn phase_vjp, psf_fft_vjp, psf_periodic_vjp;
+apply_ws_fn phase_apply, psf_fft_apply;
+vjp_ws_fn phase_vjp, psf_fft_vjp;
 pinv_ws_fn psf_periodic_pinv;
 pgdm_prepare_fn psf_periodic_pgdm_prepare;
 pgdm_residual_fn psf_periodic_pgdm_residual;

@@ -25,6 +25,9 @@
 // and writes each of its column tiles as ONE contiguous run of TC * H complex numbers.
 // 2 * batch * C * Nw * H floats, 8-byte aligned.
 //
+// The host section at the end forms every launch with fft_stage (sp_fft.h): the grid from the
+// tiles per sample and the batch, the LDS size from the transform length, the launch check.
+//
 // FFT (the core lives in sp_fft.h, shared with sp_psf_fft.hip): Stockham autosort, decimation in
 // time, between two LDS buffers (one barrier per pass):
 // radix-4 passes, one radix-2 pass when log2 is odd, and the radix-3 pass last, so every pass's
@@ -268,20 +271,25 @@ int64_t phase_workspace(const sp_op* op, int64_t batch) {
     return 2 * batch * g.C * (int64_t)g.Nw * g.H;
 }
 
-// rows (x -> ws), then the column pass of MODE: PH_APPLY (-> y) or PH_VJP (gy -> ws)
+// The launches go through fft_stage (sp_fft.h).  rows (x -> ws), then the column pass of MODE:
+// PH_APPLY (-> y) or PH_VJP (gy -> ws)
 template <int MODE>
 static int phase_forward(const char* what, const sp_op* op, const float* x, const float* gy, float* y,
                          int64_t batch, float2* ws, hipStream_t s) {
     const phase_geom g(*op);
-    launch_w(0, 0.0, k_phase_rows<false>, sample_grid(op->channels * phase_row_tiles(op), batch),
-             dim3(kBlock), phase_lds_bytes(g.Nw), s, *op, x, (const float*)nullptr, 1.f, 0.f, ws,
-             phase_lines(g.Nw), (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    const int rc = check_launch(what);
+    const int rc = fft_stage(what, 0, 0.0, k_phase_rows<false>, g.C * phase_row_tiles(op), batch, g.Nw,
+                             s, *op, x, kNoIn, 1.f, 0.f, ws, phase_lines(g.Nw), kNoSched, kNoCursor);
     if (rc != SP_OK) return rc;
-    launch_w(0, 0.0, k_phase_cols<MODE>, sample_grid(op->channels * phase_col_tiles(op), batch),
-             dim3(kBlock), phase_lds_bytes(g.Nh), s, *op, ws, gy, (int64_t)1, 0.f, y, (float*)nullptr, 0,
-             phase_lines(g.Nh), (const sp_step_rec*)nullptr, (const int32_t*)nullptr);
-    return check_launch(what);
+    return fft_stage(what, 0, 0.0, k_phase_cols<MODE>, g.C * phase_col_tiles(op), batch, g.Nh, s, *op,
+                     ws, gy, (int64_t)1, 0.f, y, kNoOut, 0, phase_lines(g.Nh), kNoSched, kNoCursor);
+}
+
+// rows^-1 (ws -> out), the last launch of a pass
+static int phase_rows_inv(const char* what, int kind, const sp_op* op, const float2* ws, float* out,
+                          int64_t batch, hipStream_t s) {
+    const phase_geom g(*op);
+    return fft_stage(what, kind, 0.0, k_phase_rows_inv, g.C * phase_row_tiles(op), batch, g.Nw, s, *op,
+                     ws, out, phase_lines(g.Nw));
 }
 
 int phase_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
@@ -294,31 +302,23 @@ int phase_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64
               float* work, hipStream_t s) {
     float2* ws = reinterpret_cast<float2*>(work);
     const int rc = phase_forward<PH_VJP>("sp_op_vjp_ws", op, x, gy, nullptr, batch, ws, s);
-    if (rc != SP_OK) return rc;
-    const int Nw = phase_geom(*op).Nw;
-    launch_w(0, 0.0, k_phase_rows_inv, sample_grid(op->channels * phase_row_tiles(op), batch),
-             dim3(kBlock), phase_lds_bytes(Nw), s, *op, (const float2*)ws, dx, phase_lines(Nw));
-    return check_launch("sp_op_vjp_ws");
+    return rc == SP_OK ? phase_rows_inv("sp_op_vjp_ws", 0, op, ws, dx, batch, s) : rc;
 }
 
 // rows (x, eps -> work), columns (work, y -> work, partials), rows^-1 (work -> v)
 int phase_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
     const phase_geom g(*op);
+    const char* what = "sp_dps_residual_ws";
     float2* ws = reinterpret_cast<float2*>(r.work);
     const int P = static_cast<int>(phase_partials(op));
-    const dim3 rows = sample_grid(op->channels * phase_row_tiles(op), r.batch);
-    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_phase_rows<true>, rows, dim3(kBlock),
-             phase_lds_bytes(g.Nw), s, *op, r.x, r.eps, r.a, r.k, ws, phase_lines(g.Nw), r.sched, r.cursor);
-    int rc = check_launch("sp_dps_residual_ws");
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_phase_cols<PH_RESIDUAL>, sample_grid(P, r.batch), dim3(kBlock),
-             phase_lds_bytes(g.Nh), s, *op, ws, r.y, r.y_div, r.gs, (float*)nullptr, r.partial, P,
-             phase_lines(g.Nh), r.sched, r.cursor);
-    rc = check_launch("sp_dps_residual_ws");
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_phase_rows_inv, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, *op,
-             (const float2*)ws, r.v, phase_lines(g.Nw));
-    return check_launch("sp_dps_residual_ws");
+    int rc = fft_stage(what, TK_DPS_RESIDUAL, (double)r.batch, k_phase_rows<true>,
+                       g.C * phase_row_tiles(op), r.batch, g.Nw, s, *op, r.x, r.eps, r.a, r.k, ws,
+                       phase_lines(g.Nw), r.sched, r.cursor);
+    if (rc == SP_OK)
+        rc = fft_stage(what, TK_DPS_RESIDUAL, 0.0, k_phase_cols<PH_RESIDUAL>, P, r.batch, g.Nh, s, *op,
+                       ws, r.y, r.y_div, r.gs, kNoOut, r.partial, P, phase_lines(g.Nh), r.sched,
+                       r.cursor);
+    return rc == SP_OK ? phase_rows_inv(what, TK_DPS_RESIDUAL, op, ws, r.v, r.batch, s) : rc;
 }
 
 }  // namespace sp

@@ -37,9 +37,9 @@
 // (plane, row tile) is block_sum's fixed order: the bits do not depend on the batch, y_div or the
 // shard.  Plain stores, no atomics.
 //
-// SP_OP_PSF_PERIODIC (at the end of the file) runs the same kernels on exact-size transforms,
-// Nh = H and Nw = W, where the wrap-around blur is diagonal: nothing extended or folded, and a
-// pseudo-inverse that is one more multiplier.
+// SP_OP_PSF_PERIODIC runs the same kernels on exact-size transforms, Nh = H and Nw = W, where the
+// wrap-around blur is diagonal: nothing extended or folded, and a pseudo-inverse that is one more
+// multiplier.  The host section at the end of the file launches both kinds through one pipeline.
 
 #include <algorithm>
 
@@ -60,20 +60,10 @@ static int pf_size(int n) {
     return 0;
 }
 
-struct pf_geom {  // filled on the host from a valid descriptor
+struct pf_geom {  // filled on the host from a valid descriptor (pf_geometry)
     int C, H, W, R, mode, Nh, Nw, HW;  // HW = Nw / 2 + 1 stored columns
     const float2* spec;                // [HW][Nh]
 };
-
-static pf_geom pf_geometry(const sp_op* op) {
-    pf_geom g;
-    g.C = op->channels, g.H = op->height, g.W = op->width, g.R = op->radius, g.mode = op->factor;
-    g.Nh = pf_size(op->height + 2 * op->radius);
-    g.Nw = pf_size(op->width + 2 * op->radius);
-    g.HW = g.Nw / 2 + 1;
-    g.spec = reinterpret_cast<const float2*>(op->taps);
-    return g;
-}
 
 // source pixel of extended position p in [0, n + 2R) along an axis of n pixels; -1: a zero
 __device__ __forceinline__ int pf_src(int p, int R, int n, int mode) {
@@ -349,6 +339,20 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
 // ---------------------------------------------------------------------------
 // host side (called from the entry points in sp_dps.hip; `op` is valid)
 // ---------------------------------------------------------------------------
+// SP_OP_PSF_PERIODIC is the wrap-around correlation on an image whose own sizes are transform
+// lengths (Nh = H, Nw = W).  The blur is then exactly diagonal in the transform the kernels
+// compute: A = IFFT2 M FFT2 with M = conj(FFT2(h centred at [0, 0])), so nothing is extended or
+// folded, A^T has the multiplier conj(M), and the pseudo-inverse truncated to the kept frequencies
+// has P = kept ? 1 / M : 0 (operators/periodic.py; both computed in fp64 by the caller).
+// op.taps = M then P, each (re, im) pairs [W / 2 + 1][H].
+//
+// Both kinds run one pipeline: a pf_run (the entry point's name and timing kind, the geometry, the
+// kernels' EXT) and the three stages pf_rows, pf_cols, pf_rows_inv / pf_rows_residual, which pick
+// the kernel instantiation and go through fft_stage (sp_fft.h).  PSF_FFT has EXT = true on pf_size
+// transforms (but for the row stage of A^T, which stages the rows as they are), PSF_PERIODIC
+// EXT = false on exact-size ones with the multiplier M or P; pf_map and
+// psf_fft_dps_residual are the only launch sequences of the maps and of DPS pass 1.  Every pass
+// starts with pf_rows, which carries a timed pass's work (the batch); the later stages carry 0.
 bool psf_fft_valid(const sp_op* op) {  // radius = R, factor = padding mode, taps = the spectrum
     if (!op->taps || op->keep_bits || op->word_rank || op->factor < 0 || op->factor > 2 ||
         op->channels <= 0 || op->height <= 0 || op->width <= 0 || op->radius < 1 ||
@@ -358,6 +362,31 @@ bool psf_fft_valid(const sp_op* op) {  // radius = R, factor = padding mode, tap
     return (int64_t)op->channels * op->height * op->width == op->n && op->m == op->n &&
            phase_size_ok(pf_size(op->height + 2 * op->radius)) &&
            phase_size_ok(pf_size(op->width + 2 * op->radius));
+}
+
+bool psf_periodic_valid(const sp_op* op) {  // radius = R, factor = 0, taps = M then P
+    if (!op->taps || op->keep_bits || op->word_rank || op->factor != 0 || op->channels <= 0 ||
+        !phase_size_ok(op->height) || !phase_size_ok(op->width) || op->radius < 1 ||
+        op->radius > (std::min(op->height, op->width) - 1) / 2)  // 2R + 1 <= min(H, W)
+        return false;
+    return (int64_t)op->channels * op->height * op->width == op->n && op->m == op->n;
+}
+
+enum { PP_SPEC_M = 0, PP_SPEC_P = 1 };  // the periodic kind's multipliers in op.taps
+
+static inline bool pf_extends(const sp_op* op) { return op->kind == SP_OP_PSF_FFT; }
+
+// `which`: the multiplier of the periodic kind; PSF_FFT has the one spectrum
+static pf_geom pf_geometry(const sp_op* op, int which = PP_SPEC_M) {
+    const bool ext = pf_extends(op);
+    pf_geom g;
+    g.C = op->channels, g.H = op->height, g.W = op->width, g.R = op->radius;
+    g.mode = ext ? op->factor : PF_CIRCULAR;
+    g.Nh = ext ? pf_size(op->height + 2 * op->radius) : op->height;
+    g.Nw = ext ? pf_size(op->width + 2 * op->radius) : op->width;
+    g.HW = g.Nw / 2 + 1;
+    g.spec = reinterpret_cast<const float2*>(op->taps) + (int64_t)which * g.HW * g.Nh;
+    return g;
 }
 
 static inline int pf_row_tiles(const pf_geom& g) {
@@ -380,178 +409,109 @@ int64_t psf_fft_workspace(const sp_op* op, int64_t batch) {
     return 2 * batch * g.C * (int64_t)g.HW * g.H;
 }
 
-static const sp_step_rec* const kNoSched = nullptr;
-static const int32_t* const kNoCursor = nullptr;
-static const float2* const kNoSpec = nullptr;
+struct pf_run {  // one entry point's pass of `batch` samples through the intermediate `ws`
+    const char* what;
+    int kind;  // timing kind, 0: untimed
+    pf_geom g;
+    bool ext;
+    int64_t batch;
+    float2* ws;
+    hipStream_t s;
+};
 
-// rows, columns, rows^-1 of A (ADJ false) or A^T (true): in -> work -> out
-template <bool ADJ>
-static int pf_map(const char* what, const sp_op* op, const float* in, float* out, int64_t batch,
-                  float* work, hipStream_t s) {
-    const pf_geom g = pf_geometry(op);
-    float2* ws = reinterpret_cast<float2*>(work);
-    const dim3 rows = sample_grid(g.C * pf_row_tiles(g), batch);
-    launch_w(0, 0.0, k_pf_rows<false, !ADJ>, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, g, in,
-             (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), kNoSched, kNoCursor);
-    int rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(0, 0.0, k_pf_cols<ADJ>, sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock),
-             phase_lds_bytes(g.Nh), s, g, ws, phase_lines(g.Nh), kNoSpec, (int64_t)1, 0.f);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(0, 0.0, k_pf_rows_inv<ADJ ? PF_OUT_AT : PF_OUT_A>, rows, dim3(kBlock),
-             phase_lds_bytes(g.Nw), s, g, ws, out, (const float*)nullptr, (int64_t)1, 0.f,
-             (float*)nullptr, 0, phase_lines(g.Nw), kNoSched, kNoCursor);
-    return check_launch(what);
+static pf_run pf_begin(const char* what, int kind, const sp_op* op, int which, int64_t batch,
+                       float* work, hipStream_t s) {
+    return {what, kind, pf_geometry(op, which), pf_extends(op), batch,
+            reinterpret_cast<float2*>(work), s};
+}
+
+struct pf_x0 {  // the DPS form of the row stage: x0 = (in - k eps) / a, or sched[*cursor]'s a, k
+    const float* eps;
+    float a, k;
+    const sp_step_rec* sched;
+    const int32_t* cursor;
+};
+
+// launch 1: in (x0 of in, eps) -> ws; the rows are extended for A where the kind extends, and
+// staged as they are for A^T (adj)
+static int pf_rows(const pf_run& p, bool adj, const float* in, const pf_x0* x0 = nullptr) {
+    const pf_geom& g = p.g;
+    const pf_x0 f = x0 ? *x0 : pf_x0{kNoIn, 1.f, 0.f, kNoSched, kNoCursor};
+    const bool ext = p.ext && !adj;
+    const auto kern = x0 ? (ext ? k_pf_rows<true, true> : k_pf_rows<true, false>)
+                         : (ext ? k_pf_rows<false, true> : k_pf_rows<false, false>);
+    return fft_stage(p.what, p.kind, p.kind ? (double)p.batch : 0.0, kern, g.C * pf_row_tiles(g),
+                     p.batch, g.Nw, p.s, g, in, f.eps, f.a, f.k, p.ws, phase_lines(g.Nw), f.sched,
+                     f.cursor);
+}
+
+// launch 2 on ws: A or A^T (adj) of the map, or a form of the periodic kind with its arguments
+static int pf_cols(const pf_run& p, bool adj, int form = PF_COL_MAP, const float2* qs = nullptr,
+                   int64_t y_div = 1, float gs = 0.f) {
+    const pf_geom& g = p.g;
+    const auto kern = form == PF_COL_PREPARE ? k_pf_cols<false, false, PF_COL_PREPARE>
+                      : form == PF_COL_PGDM  ? k_pf_cols<false, false, PF_COL_PGDM>
+                      : p.ext                ? (adj ? k_pf_cols<true> : k_pf_cols<false>)
+                                             : (adj ? k_pf_cols<true, false> : k_pf_cols<false, false>);
+    return fft_stage(p.what, p.kind, 0.0, kern, g.C * pf_col_tiles(g), p.batch, g.Nh, p.s, g, p.ws,
+                     phase_lines(g.Nh), qs, y_div, gs);
+}
+
+// launch 3: ws -> out, folded where the kind extends and the map is A^T
+static int pf_rows_inv(const pf_run& p, bool adj, float* out) {
+    const pf_geom& g = p.g;
+    const auto kern = adj && p.ext ? k_pf_rows_inv<PF_OUT_AT> : k_pf_rows_inv<PF_OUT_A>;
+    return fft_stage(p.what, p.kind, 0.0, kern, g.C * pf_row_tiles(g), p.batch, g.Nw, p.s, g, p.ws,
+                     out, kNoIn, (int64_t)1, 0.f, kNoOut, 0, phase_lines(g.Nw), kNoSched, kNoCursor);
+}
+
+// the fused launch 3 + 1 of DPS pass 1: ws, r.y -> ws, r.partial
+static int pf_rows_residual(const pf_run& p, const dps_residual_args& r) {
+    const pf_geom& g = p.g;
+    const int P = g.C * pf_row_tiles(g);
+    return fft_stage(p.what, p.kind, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, P, p.batch, g.Nw, p.s, g,
+                     p.ws, kNoOut, r.y, r.y_div, r.gs, r.partial, P, phase_lines(g.Nw), r.sched,
+                     r.cursor);
+}
+
+// rows, columns, rows^-1 of the map with p's spectrum or of its transpose (adj): in -> ws -> out
+static int pf_map(const pf_run& p, bool adj, const float* in, float* out) {
+    int rc = pf_rows(p, adj, in);
+    if (rc == SP_OK) rc = pf_cols(p, adj);
+    if (rc == SP_OK) rc = pf_rows_inv(p, adj, out);
+    return rc;
 }
 
 int psf_fft_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
                   hipStream_t s) {
-    return pf_map<false>("sp_op_apply_ws", op, x, y, batch, work, s);
+    return pf_map(pf_begin("sp_op_apply_ws", 0, op, PP_SPEC_M, batch, work, s), false, x, y);
 }
 
 // the map is linear: A^T gy, x is not read
 int psf_fft_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
                 float* work, hipStream_t s) {
     (void)x;
-    return pf_map<true>("sp_op_vjp_ws", op, gy, dx, batch, work, s);
-}
-
-// rows (x, eps -> work), columns A, rows^-1 + rows (work, y -> work, partials), columns A^T,
-// rows^-1 A^T (work -> v)
-int psf_fft_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
-    const pf_geom g = pf_geometry(op);
-    float2* ws = reinterpret_cast<float2*>(r.work);
-    const int P = static_cast<int>(psf_fft_partials(op));
-    const int TR = phase_lines(g.Nw), TC = phase_lines(g.Nh);
-    const size_t lr = phase_lds_bytes(g.Nw), lc = phase_lds_bytes(g.Nh);
-    const dim3 rows = sample_grid(P, r.batch), cols = sample_grid(g.C * pf_col_tiles(g), r.batch);
-    const char* what = "sp_dps_residual_ws";
-    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_pf_rows<true, true>, rows, dim3(kBlock), lr, s, g,
-             r.x, r.eps, r.a, r.k, ws, TR, r.sched, r.cursor);
-    int rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false>, cols, dim3(kBlock), lc, s, g, ws, TC, kNoSpec,
-             (int64_t)1, 0.f);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, rows, dim3(kBlock), lr, s, g, ws,
-             (float*)nullptr, r.y, r.y_div, r.gs, r.partial, P, TR, r.sched, r.cursor);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<true>, cols, dim3(kBlock), lc, s, g, ws, TC, kNoSpec,
-             (int64_t)1, 0.f);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_AT>, rows, dim3(kBlock), lr, s, g, ws, r.v,
-             (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, TR, kNoSched, kNoCursor);
-    return check_launch(what);
-}
-
-// ---------------------------------------------------------------------------
-// SP_OP_PSF_PERIODIC: the wrap-around correlation on an image whose own sizes are transform
-// lengths (Nh = H, Nw = W).  The blur is then exactly diagonal in the transform the kernels
-// compute: A = IFFT2 M FFT2 with M = conj(FFT2(h centred at [0, 0])), so nothing is extended or
-// folded, A^T has the multiplier conj(M), and the pseudo-inverse truncated to the kept frequencies
-// has P = kept ? 1 / M : 0 (operators/periodic.py; both computed in fp64 by the caller).
-// op.taps = M then P, each (re, im) pairs [W / 2 + 1][H].  The launches are the ones above with
-// EXT = false: rows<., false>, cols<., false, .>, rows_inv<PF_OUT_A | PF_OUT_RESIDUAL>.
-// ---------------------------------------------------------------------------
-enum { PP_SPEC_M = 0, PP_SPEC_P = 1 };
-
-bool psf_periodic_valid(const sp_op* op) {  // radius = R, factor = 0, taps = M then P
-    if (!op->taps || op->keep_bits || op->word_rank || op->factor != 0 || op->channels <= 0 ||
-        !phase_size_ok(op->height) || !phase_size_ok(op->width) || op->radius < 1 ||
-        op->radius > (std::min(op->height, op->width) - 1) / 2)  // 2R + 1 <= min(H, W)
-        return false;
-    return (int64_t)op->channels * op->height * op->width == op->n && op->m == op->n;
-}
-
-static pf_geom pp_geometry(const sp_op* op, int which) {
-    pf_geom g;
-    g.C = op->channels, g.H = op->height, g.W = op->width, g.R = op->radius, g.mode = PF_CIRCULAR;
-    g.Nh = op->height, g.Nw = op->width;
-    g.HW = g.Nw / 2 + 1;
-    g.spec = reinterpret_cast<const float2*>(op->taps) + (int64_t)which * g.HW * g.Nh;
-    return g;
-}
-
-int64_t psf_periodic_partials(const sp_op* op) {
-    return (int64_t)op->channels * pf_row_tiles(pp_geometry(op, PP_SPEC_M));
-}
-
-int64_t psf_periodic_workspace(const sp_op* op, int64_t batch) {
-    const pf_geom g = pp_geometry(op, PP_SPEC_M);
-    return 2 * batch * g.C * (int64_t)g.HW * g.H;
-}
-
-// rows, columns, rows^-1 with the multiplier g.spec (CONJ: its conjugate): in -> work -> out
-template <bool CONJ>
-static int pp_map(const char* what, const pf_geom& g, const float* in, float* out, int64_t batch,
-                  float* work, hipStream_t s) {
-    float2* ws = reinterpret_cast<float2*>(work);
-    const dim3 rows = sample_grid(g.C * pf_row_tiles(g), batch);
-    launch_w(0, 0.0, k_pf_rows<false, false>, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, g, in,
-             (const float*)nullptr, 1.f, 0.f, ws, phase_lines(g.Nw), kNoSched, kNoCursor);
-    int rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(0, 0.0, k_pf_cols<CONJ, false>, sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock),
-             phase_lds_bytes(g.Nh), s, g, ws, phase_lines(g.Nh), kNoSpec, (int64_t)1, 0.f);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(0, 0.0, k_pf_rows_inv<PF_OUT_A>, rows, dim3(kBlock), phase_lds_bytes(g.Nw), s, g, ws,
-             out, (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, phase_lines(g.Nw),
-             kNoSched, kNoCursor);
-    return check_launch(what);
-}
-
-int psf_periodic_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
-                       hipStream_t s) {
-    return pp_map<false>("sp_op_apply_ws", pp_geometry(op, PP_SPEC_M), x, y, batch, work, s);
-}
-
-int psf_periodic_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
-                     float* work, hipStream_t s) {
-    (void)x;
-    return pp_map<true>("sp_op_vjp_ws", pp_geometry(op, PP_SPEC_M), gy, dx, batch, work, s);
+    return pf_map(pf_begin("sp_op_vjp_ws", 0, op, PP_SPEC_M, batch, work, s), true, gy, dx);
 }
 
 // A^+ (multiplier P) or its transpose (conj(P))
 int psf_periodic_pinv(const sp_op* op, const float* y, float* x, int64_t batch, int transpose,
                       float* work, hipStream_t s) {
-    const pf_geom g = pp_geometry(op, PP_SPEC_P);
-    return transpose ? pp_map<true>("sp_op_pinv_ws", g, y, x, batch, work, s)
-                     : pp_map<false>("sp_op_pinv_ws", g, y, x, batch, work, s);
+    return pf_map(pf_begin("sp_op_pinv_ws", 0, op, PP_SPEC_P, batch, work, s), transpose != 0, y, x);
 }
 
-// the five launches of psf_fft_dps_residual on exact-size transforms
-int psf_periodic_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
-    const pf_geom g = pp_geometry(op, PP_SPEC_M);
-    float2* ws = reinterpret_cast<float2*>(r.work);
-    const int P = static_cast<int>(psf_periodic_partials(op));
-    const int TR = phase_lines(g.Nw), TC = phase_lines(g.Nh);
-    const size_t lr = phase_lds_bytes(g.Nw), lc = phase_lds_bytes(g.Nh);
-    const dim3 rows = sample_grid(P, r.batch), cols = sample_grid(g.C * pf_col_tiles(g), r.batch);
-    const char* what = "sp_dps_residual_ws";
-    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_pf_rows<true, false>, rows, dim3(kBlock), lr, s, g,
-             r.x, r.eps, r.a, r.k, ws, TR, r.sched, r.cursor);
-    int rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false, false>, cols, dim3(kBlock), lc, s, g, ws, TC,
-             kNoSpec, (int64_t)1, 0.f);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, rows, dim3(kBlock), lr, s, g, ws,
-             (float*)nullptr, r.y, r.y_div, r.gs, r.partial, P, TR, r.sched, r.cursor);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<true, false>, cols, dim3(kBlock), lc, s, g, ws, TC,
-             kNoSpec, (int64_t)1, 0.f);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_A>, rows, dim3(kBlock), lr, s, g, ws, r.v,
-             (const float*)nullptr, (int64_t)1, 0.f, (float*)nullptr, 0, TR, kNoSched, kNoCursor);
-    return check_launch(what);
+// rows (x, eps -> work), columns A, rows^-1 + rows (work, y -> work, partials), columns A^T,
+// rows^-1 A^T (work -> v)
+int psf_fft_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    const pf_run p =
+        pf_begin("sp_dps_residual_ws", TK_DPS_RESIDUAL, op, PP_SPEC_M, r.batch, r.work, s);
+    const pf_x0 x0 = {r.eps, r.a, r.k, r.sched, r.cursor};
+    int rc = pf_rows(p, false, r.x, &x0);
+    if (rc == SP_OK) rc = pf_cols(p, false);
+    if (rc == SP_OK) rc = pf_rows_residual(p, r);
+    if (rc == SP_OK) rc = pf_cols(p, true);
+    if (rc == SP_OK) rc = pf_rows_inv(p, true, r.v);
+    return rc;
 }
 
 // Q = P * FFT2(y) / (H W) per observation row, in the intermediate's layout: rows, then the
@@ -559,18 +519,9 @@ int psf_periodic_dps_residual(const sp_op* op, const dps_residual_args& r, hipSt
 // runs once and every step's column launch reads Q instead of transforming y again.
 int psf_periodic_pgdm_prepare(const sp_op* op, const float* y, int64_t rows_y, float* q,
                               hipStream_t s) {
-    const pf_geom g = pp_geometry(op, PP_SPEC_P);
-    float2* qs = reinterpret_cast<float2*>(q);
-    const char* what = "sp_pgdm_prepare";
-    launch_w(0, 0.0, k_pf_rows<false, false>, sample_grid(g.C * pf_row_tiles(g), rows_y),
-             dim3(kBlock), phase_lds_bytes(g.Nw), s, g, y, (const float*)nullptr, 1.f, 0.f, qs,
-             phase_lines(g.Nw), kNoSched, kNoCursor);
-    const int rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(0, 0.0, k_pf_cols<false, false, PF_COL_PREPARE>,
-             sample_grid(g.C * pf_col_tiles(g), rows_y), dim3(kBlock), phase_lds_bytes(g.Nh), s, g,
-             qs, phase_lines(g.Nh), kNoSpec, (int64_t)1, 0.f);
-    return check_launch(what);
+    const pf_run p = pf_begin("sp_pgdm_prepare", 0, op, PP_SPEC_P, rows_y, q, s);
+    const int rc = pf_rows(p, false, y);
+    return rc == SP_OK ? pf_cols(p, false, PF_COL_PREPARE) : rc;
 }
 
 // v = gs (A^+ y - Pi x0): rows (x, eps -> work), columns (z <- gs (Q - kept z) between the
@@ -578,24 +529,13 @@ int psf_periodic_pgdm_prepare(const sp_op* op, const float* y, int64_t rows_y, f
 int psf_periodic_pgdm_residual(const sp_op* op, const float* x, const float* eps, const float* q,
                                int64_t batch, int64_t y_div, const sp_dps_coefs& c, float* v,
                                float* work, hipStream_t s) {
-    const pf_geom g = pp_geometry(op, PP_SPEC_P);
-    float2* ws = reinterpret_cast<float2*>(work);
-    const dim3 rows = sample_grid(g.C * pf_row_tiles(g), batch);
-    const char* what = "sp_pgdm_residual_ws";
-    launch_w(TK_DPS_RESIDUAL, (double)batch, k_pf_rows<true, false>, rows, dim3(kBlock),
-             phase_lds_bytes(g.Nw), s, g, x, eps, c.a, c.k, ws, phase_lines(g.Nw), kNoSched,
-             kNoCursor);
-    int rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_cols<false, false, PF_COL_PGDM>,
-             sample_grid(g.C * pf_col_tiles(g), batch), dim3(kBlock), phase_lds_bytes(g.Nh), s, g,
-             ws, phase_lines(g.Nh), reinterpret_cast<const float2*>(q), y_div, c.grad_scale);
-    rc = check_launch(what);
-    if (rc != SP_OK) return rc;
-    launch_w(TK_DPS_RESIDUAL, 0.0, k_pf_rows_inv<PF_OUT_A>, rows, dim3(kBlock),
-             phase_lds_bytes(g.Nw), s, g, ws, v, (const float*)nullptr, (int64_t)1, 0.f,
-             (float*)nullptr, 0, phase_lines(g.Nw), kNoSched, kNoCursor);
-    return check_launch(what);
+    const pf_run p = pf_begin("sp_pgdm_residual_ws", TK_DPS_RESIDUAL, op, PP_SPEC_P, batch, work, s);
+    const pf_x0 x0 = {eps, c.a, c.k, kNoSched, kNoCursor};
+    int rc = pf_rows(p, false, x, &x0);
+    if (rc == SP_OK)
+        rc = pf_cols(p, false, PF_COL_PGDM, reinterpret_cast<const float2*>(q), y_div, c.grad_scale);
+    if (rc == SP_OK) rc = pf_rows_inv(p, false, v);
+    return rc;
 }
 
 }  // namespace sp

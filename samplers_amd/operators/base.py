@@ -4,13 +4,21 @@ An ``Operator`` is an ``nn.Module`` holding its long-lived tensors as buffers.
 Operators that the HIP library implements natively also expose
 ``hip_descriptor()`` -> :class:`samplers_amd._hip.SpOp`, which the fused DPS
 kernels consume; on device tensors their ``apply`` / ``apply_transpose`` run
-HIP kernels (differentiable through :class:`HipLinearMap`).  On host tensors
-they run plain torch ops — only setup code (shape inference, synthetic
-observations) touches that path.
+HIP kernels (differentiable through :class:`HipLinearMap`, or through
+:class:`HipWorkspaceMap` for the linear kinds whose maps need a workspace: the
+FFT blurs).  On host tensors they run plain torch ops — only setup code (shape
+inference, synthetic observations) touches that path.
+
+The helpers the operator modules share live here too: the workspace of a map
+(``_work``), the lengths the in-LDS FFT kernels transform (``transform_size_ok``,
+``MIN_SIZE``, ``MAX_SIZE``), the transpose of a host map through autograd
+(``_transpose_by_grad``) and the descriptor of a plane-to-plane kind
+(``_plane_descriptor``).
 """
 
 from __future__ import annotations
 
+import math
 from abc import ABC, abstractmethod
 
 import torch
@@ -111,3 +119,80 @@ def _hip_linear(op: Operator, t: Tensor, transpose: bool) -> Tensor:
         _hip.check(fn(desc, _hip.ptr(flat), _hip.ptr(out), flat.shape[0], _hip.stream_of(t)),
                    "sp_op_adjoint" if transpose else "sp_op_apply")
     return out.reshape(*batch, *out_shape)
+
+
+def _work(lib, desc, batch: int, like: Tensor) -> Tensor:
+    """The workspace of ``sp_op_apply_ws`` / ``sp_op_vjp_ws`` / ``sp_op_pinv_ws`` for ``batch``."""
+    floats = int(lib.sp_op_workspace(desc, batch))
+    if floats < 0:
+        raise _hip.HipLibraryError(f"sp_op_workspace rejected the descriptor ({floats})")
+    return torch.empty(max(floats, 2), device=like.device, dtype=torch.float32)
+
+
+class HipWorkspaceMap(torch.autograd.Function):
+    """A linear map with ``y_shape == x_shape`` that runs through a workspace:
+    ``forward(op, t, pinv, transpose)`` is ``sp_op_apply_ws`` (A), ``sp_op_vjp_ws`` (Aᵀ) or
+    ``sp_op_pinv_ws`` (A⁺, A⁺ᵀ); the backward of a linear map is its transpose, so it
+    differentiates to any order."""
+
+    @staticmethod
+    def forward(ctx, op: Operator, t: Tensor, pinv: bool, transpose: bool) -> Tensor:
+        ctx.op, ctx.pinv, ctx.transpose = op, pinv, transpose
+        return _hip_workspace_map(op, t, pinv, transpose)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return None, HipWorkspaceMap.apply(ctx.op, g.to(torch.float32).contiguous(), ctx.pinv,
+                                           not ctx.transpose), None, None
+
+
+def _hip_workspace_map(op: Operator, t: Tensor, pinv: bool, transpose: bool) -> Tensor:
+    _hip.require_cuda(t, type(op).__name__)
+    if t.dtype != torch.float32:
+        raise _hip.HipLibraryError(f"{type(op).__name__}: HIP operators compute in fp32")
+    lib, desc = _hip.load_library(), op.hip_descriptor()
+    flat, batch = _flatten_batch(t.detach(), op.x_shape)
+    out = torch.empty_like(flat)
+    n = flat.shape[0]
+    if n > 0:
+        work, stream = _work(lib, desc, n, flat), _hip.stream_of(t)
+        if pinv:
+            _hip.check(lib.sp_op_pinv_ws(desc, _hip.ptr(flat), _hip.ptr(out), n, int(transpose),
+                                         _hip.ptr(work), stream), "sp_op_pinv_ws")
+        elif transpose:  # A^T: the x argument of sp_op_vjp_ws is not read
+            _hip.check(lib.sp_op_vjp_ws(desc, _hip.ptr(flat), _hip.ptr(flat), _hip.ptr(out), n,
+                                        _hip.ptr(work), stream), "sp_op_vjp_ws")
+        else:
+            _hip.check(lib.sp_op_apply_ws(desc, _hip.ptr(flat), _hip.ptr(out), n, _hip.ptr(work),
+                                          stream), "sp_op_apply_ws")
+    return out.reshape(*batch, *op.x_shape)
+
+
+MIN_SIZE, MAX_SIZE = 8, 1024
+
+
+def transform_size_ok(n: int) -> bool:
+    """``n`` is ``2^k`` or ``3·2^k`` in ``[MIN_SIZE, MAX_SIZE]``: a length the kernels transform."""
+    n = int(n)
+    if n < MIN_SIZE or n > MAX_SIZE:
+        return False
+    while n % 2 == 0:
+        n //= 2
+    return n in (1, 3)
+
+
+def _transpose_by_grad(fn, y: Tensor) -> Tensor:
+    """``Aᵀ y`` of a differentiable linear host map ``fn`` whose output has its input's shape."""
+    x = torch.zeros_like(y, requires_grad=True)
+    with torch.enable_grad():
+        (g,) = torch.autograd.grad(fn(x), x, grad_outputs=y)
+    return g
+
+
+def _plane_descriptor(kind: int, x_shape: Shape) -> "_hip.SpOp":
+    """The descriptor of a kind on ``(C, H, W)`` planes with ``n = m = C·H·W``."""
+    d = _hip.SpOp()
+    d.kind = kind
+    d.channels, d.height, d.width = x_shape
+    d.n = d.m = int(math.prod(x_shape))
+    return d

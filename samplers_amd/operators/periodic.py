@@ -30,28 +30,20 @@ tensors A is ``F.pad`` / ``F.conv2d`` and A⁺ is ``torch.fft`` with the stored 
 
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import _flatten_batch
-from .blur import gaussian_taps
+from .base import (MAX_SIZE, MIN_SIZE, HipWorkspaceMap, _plane_descriptor, _transpose_by_grad,
+                   transform_size_ok)
 from .linear import LinearOperator
-from .psf_fft import MAX_SIZE, MIN_SIZE, _square_kernel, _work, psf_pad_torch
+from .psf import _gaussian_psf, _square_kernel
+from .psf_fft import psf_pad_torch
 
 
-def size_ok(n: int) -> bool:
-    """``n`` is ``2^k`` or ``3·2^k`` in ``[MIN_SIZE, MAX_SIZE]``: a length the kernels transform."""
-    n = int(n)
-    if n < MIN_SIZE or n > MAX_SIZE:
-        return False
-    while n % 2 == 0:
-        n //= 2
-    return n in (1, 3)
+size_ok = transform_size_ok
 
 
 def transfer_function(kernel, H: int, W: int) -> Tensor:
@@ -92,43 +84,6 @@ def half_spectrum(S) -> Tensor:
     s = np.asarray(S.detach().cpu().numpy() if isinstance(S, torch.Tensor) else S)
     s = np.ascontiguousarray(s[:, : s.shape[1] // 2 + 1].T)
     return torch.from_numpy(np.stack([s.real, s.imag], axis=-1).astype(np.float32))
-
-
-def _hip_map(op: "PeriodicBlurOperator", t: Tensor, pinv: bool, transpose: bool) -> Tensor:
-    _hip.require_cuda(t, type(op).__name__)
-    if t.dtype != torch.float32:
-        raise _hip.HipLibraryError(f"{type(op).__name__}: HIP operators compute in fp32")
-    lib, desc = _hip.load_library(), op.hip_descriptor()
-    flat, batch = _flatten_batch(t.detach(), op.x_shape)
-    out = torch.empty_like(flat)
-    n = flat.shape[0]
-    if n > 0:
-        work, stream = _work(lib, desc, n, flat), _hip.stream_of(t)
-        if pinv:
-            _hip.check(lib.sp_op_pinv_ws(desc, _hip.ptr(flat), _hip.ptr(out), n, int(transpose),
-                                         _hip.ptr(work), stream), "sp_op_pinv_ws")
-        elif transpose:  # A^T: the x argument of sp_op_vjp_ws is not read
-            _hip.check(lib.sp_op_vjp_ws(desc, _hip.ptr(flat), _hip.ptr(flat), _hip.ptr(out), n,
-                                        _hip.ptr(work), stream), "sp_op_vjp_ws")
-        else:
-            _hip.check(lib.sp_op_apply_ws(desc, _hip.ptr(flat), _hip.ptr(out), n, _hip.ptr(work),
-                                          stream), "sp_op_apply_ws")
-    return out.reshape(*batch, *op.x_shape)
-
-
-class HipPeriodicMap(torch.autograd.Function):
-    """``forward(op, t, pinv, transpose)`` is A, Aᵀ, A⁺ or A⁺ᵀ on the ``SP_OP_PSF_PERIODIC``
-    kernels; the backward of a linear map is its transpose, so it differentiates to any order."""
-
-    @staticmethod
-    def forward(ctx, op: "PeriodicBlurOperator", t: Tensor, pinv: bool, transpose: bool) -> Tensor:
-        ctx.op, ctx.pinv, ctx.transpose = op, pinv, transpose
-        return _hip_map(op, t, pinv, transpose)
-
-    @staticmethod
-    def backward(ctx, g: Tensor):
-        return None, HipPeriodicMap.apply(ctx.op, g.to(torch.float32).contiguous(), ctx.pinv,
-                                          not ctx.transpose), None, None
 
 
 class PeriodicBlurOperator(LinearOperator):
@@ -174,41 +129,28 @@ class PeriodicBlurOperator(LinearOperator):
                  rtol: float = 3e-2, device: Device = None) -> "PeriodicBlurOperator":
         """The isotropic Gaussian PSF as the outer product of ``gaussian_taps``, as
         ``FFTPSFBlurOperator.gaussian``."""
-        if sigma <= 0:
-            raise ValueError("sigma must be positive")
-        if kernel_size % 2 != 1 or kernel_size < 3:
-            raise ValueError("kernel_size must be odd and at least 3")
-        t = gaussian_taps(kernel_size, sigma).to(torch.float64)
-        return cls(x_shape, torch.outer(t, t).to(torch.float32), rtol=rtol, device=device)
+        return cls(x_shape, _gaussian_psf(kernel_size, sigma), rtol=rtol, device=device)
 
     def apply(self, x: Tensor) -> Tensor:
         if x.is_cuda:
-            return HipPeriodicMap.apply(self, x, False, False)
+            return HipWorkspaceMap.apply(self, x, False, False)
         return psf_pad_torch(x, self.kernel, "circular")
 
     def apply_transpose(self, y: Tensor) -> Tensor:
         if y.is_cuda:
-            return HipPeriodicMap.apply(self, y, False, True)
-        x = torch.zeros_like(y, requires_grad=True)
-        with torch.enable_grad():
-            out = psf_pad_torch(x, self.kernel, "circular")
-            (g,) = torch.autograd.grad(out, x, grad_outputs=y)
-        return g
+            return HipWorkspaceMap.apply(self, y, False, True)
+        return _transpose_by_grad(lambda x: psf_pad_torch(x, self.kernel, "circular"), y)
 
     def apply_pseudo_inverse(self, y: Tensor) -> Tensor:
         if y.is_cuda:
-            return HipPeriodicMap.apply(self, y, True, False)
+            return HipWorkspaceMap.apply(self, y, True, False)
         _, h, w = self.x_shape
         p = torch.view_as_complex(self.spectra[1]).transpose(0, 1)  # (H, W // 2 + 1)
         cdtype = torch.complex128 if y.dtype == torch.float64 else torch.complex64
         return torch.fft.irfft2(torch.fft.rfft2(y) * p.to(cdtype), s=(h, w)).to(y.dtype)
 
     def hip_descriptor(self) -> _hip.SpOp:
-        c, h, w = self.x_shape
-        d = _hip.SpOp()
-        d.kind = _hip.SP_OP_PSF_PERIODIC
-        d.channels, d.height, d.width = c, h, w
-        d.n = d.m = int(math.prod(self.x_shape))
+        d = _plane_descriptor(_hip.SP_OP_PSF_PERIODIC, self.x_shape)
         d.taps = self.spectra.data_ptr()
         d.radius = self.radius
         d.factor = 0

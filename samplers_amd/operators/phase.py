@@ -35,18 +35,10 @@ import torch.nn.functional as F
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import NonlinearOperator, _flatten_batch
+from .base import (MAX_SIZE, MIN_SIZE, NonlinearOperator, _flatten_batch, _work,
+                   transform_size_ok)
 
-MIN_SIZE, MAX_SIZE = 8, 1024
-
-
-def valid_padded_size(n: int) -> bool:
-    """``n`` is ``2^k`` or ``3·2^k`` within ``[MIN_SIZE, MAX_SIZE]``."""
-    if not (MIN_SIZE <= n <= MAX_SIZE):
-        return False
-    while n % 2 == 0:
-        n //= 2
-    return n in (1, 3)
+valid_padded_size = transform_size_ok
 
 
 def nearest_valid_pads(size: int, pad: int) -> list[int]:
@@ -60,13 +52,6 @@ def nearest_valid_pads(size: int, pad: int) -> list[int]:
 def phase_torch(x: Tensor, pad_h: int, pad_w: int) -> Tensor:
     """Host (torch) form of the forward map on ``(..., C, H, W)``; differentiable."""
     return torch.fft.fft2(F.pad(x, (pad_w, pad_w, pad_h, pad_h)), norm="ortho").abs()
-
-
-def _work(lib, desc, batch: int, like: Tensor) -> Tensor:
-    floats = int(lib.sp_op_workspace(desc, batch))
-    if floats < 0:
-        raise _hip.HipLibraryError(f"sp_op_workspace rejected the descriptor ({floats})")
-    return torch.empty(max(floats, 2), device=like.device, dtype=torch.float32)
 
 
 class HipPhaseMap(torch.autograd.Function):

@@ -21,8 +21,6 @@ not the box.
 
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -30,7 +28,7 @@ import torch.nn.functional as F
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import HipLinearMap
+from .base import HipLinearMap, _plane_descriptor, _transpose_by_grad
 from .blur import gaussian_taps
 from .linear import LinearOperator
 
@@ -47,16 +45,19 @@ def psf_reflect_torch(x: Tensor, kernel: Tensor) -> Tensor:
     return out.reshape(shape)
 
 
-def _square_kernel(kernel) -> Tensor:
-    """``kernel`` as a finite fp32 ``(K, K)`` tensor, a rectangular one zero-padded and centred."""
+def _square_kernel(kernel, max_size: int | None = None) -> Tensor:
+    """``kernel`` as a finite fp32 ``(K, K)`` tensor, a rectangular one zero-padded and centred.
+    With ``max_size`` both sizes are in ``[3, max_size]``; without, the larger is at least 3."""
     k = torch.as_tensor(np.asarray(kernel) if not isinstance(kernel, torch.Tensor) else kernel)
     k = k.detach().to(device="cpu", dtype=torch.float32)
     if k.ndim != 2:
         raise ValueError("kernel must be 2-D (Kh, Kw)")
     kh, kw = int(k.shape[0]), int(k.shape[1])
-    for size in (kh, kw):
-        if size % 2 != 1 or not (3 <= size <= MAX_KERNEL_SIZE):
-            raise ValueError(f"kernel sizes must be odd and in [3, {MAX_KERNEL_SIZE}], got {(kh, kw)}")
+    if max_size is None:
+        if kh % 2 != 1 or kw % 2 != 1 or max(kh, kw) < 3:
+            raise ValueError(f"kernel sizes must be odd and the larger at least 3, got {(kh, kw)}")
+    elif any(size % 2 != 1 or not (3 <= size <= max_size) for size in (kh, kw)):
+        raise ValueError(f"kernel sizes must be odd and in [3, {max_size}], got {(kh, kw)}")
     if not bool(torch.isfinite(k).all()):
         raise ValueError("kernel values must be finite")
     size = max(kh, kw)
@@ -66,11 +67,22 @@ def _square_kernel(kernel) -> Tensor:
     return out
 
 
+def _gaussian_psf(kernel_size: int, sigma: float, max_size: int | None = None) -> Tensor:
+    """The isotropic Gaussian PSF as the outer product of ``gaussian_taps``, ``(K, K)`` fp32."""
+    if sigma <= 0:
+        raise ValueError("sigma must be positive")
+    if kernel_size % 2 != 1 or kernel_size < 3 or (max_size is not None and kernel_size > max_size):
+        raise ValueError("kernel_size must be odd and " +
+                         ("at least 3" if max_size is None else f"in [3, {max_size}]"))
+    t = gaussian_taps(kernel_size, sigma).to(torch.float64)
+    return torch.outer(t, t).to(torch.float32)
+
+
 class PSFBlurOperator(LinearOperator):
     """Depthwise blur by a dense 2-D PSF with reflect padding; ``y`` has ``x_shape``."""
 
     def __init__(self, x_shape: Shape, kernel, device: Device = None) -> None:
-        k = _square_kernel(kernel)
+        k = _square_kernel(kernel, MAX_KERNEL_SIZE)
         if len(x_shape) != 3:
             raise ValueError("x_shape must be (C, H, W)")
         r = k.shape[0] // 2
@@ -87,12 +99,7 @@ class PSFBlurOperator(LinearOperator):
                  device: Device = None) -> "PSFBlurOperator":
         """The isotropic Gaussian PSF as the outer product of ``gaussian_taps`` (the DPS
         paper's deblurring kernel is ``kernel_size=61, sigma=3``)."""
-        if sigma <= 0:
-            raise ValueError("sigma must be positive")
-        if kernel_size % 2 != 1 or not (3 <= kernel_size <= MAX_KERNEL_SIZE):
-            raise ValueError(f"kernel_size must be odd and in [3, {MAX_KERNEL_SIZE}]")
-        t = gaussian_taps(kernel_size, sigma).to(torch.float64)
-        return cls(x_shape, torch.outer(t, t).to(torch.float32), device=device)
+        return cls(x_shape, _gaussian_psf(kernel_size, sigma, MAX_KERNEL_SIZE), device=device)
 
     def apply(self, x: Tensor) -> Tensor:
         if x.is_cuda:
@@ -102,18 +109,10 @@ class PSFBlurOperator(LinearOperator):
     def apply_transpose(self, y: Tensor) -> Tensor:
         if y.is_cuda:
             return HipLinearMap.apply(self, y, True)
-        x = torch.zeros_like(y, requires_grad=True)
-        with torch.enable_grad():
-            out = psf_reflect_torch(x, self.kernel)
-            (g,) = torch.autograd.grad(out, x, grad_outputs=y)
-        return g
+        return _transpose_by_grad(lambda x: psf_reflect_torch(x, self.kernel), y)
 
     def hip_descriptor(self) -> _hip.SpOp:
-        c, h, w = self.x_shape
-        d = _hip.SpOp()
-        d.kind = _hip.SP_OP_PSF
-        d.channels, d.height, d.width = c, h, w
-        d.n = d.m = int(math.prod(self.x_shape))
+        d = _plane_descriptor(_hip.SP_OP_PSF, self.x_shape)
         d.taps = self.kernel.data_ptr()
         d.radius = self.radius
         return d

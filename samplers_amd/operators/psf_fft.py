@@ -27,8 +27,6 @@ computed once at construction, in fp64 on the host (``psf_spectrum``).
 
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -36,11 +34,10 @@ import torch.nn.functional as F
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import _flatten_batch
-from .blur import gaussian_taps
+from .base import MAX_SIZE, MIN_SIZE, HipWorkspaceMap, _plane_descriptor, _transpose_by_grad
 from .linear import LinearOperator
+from .psf import _gaussian_psf, _square_kernel
 
-MIN_SIZE, MAX_SIZE = 8, 1024
 PADDINGS = ("reflect", "circular", "zeros")  # the descriptor's `factor`: 0, 1, 2
 _PAD_MODE = {"reflect": "reflect", "circular": "circular", "zeros": "constant"}
 
@@ -85,66 +82,6 @@ def psf_pad_torch(x: Tensor, kernel: Tensor, padding: str) -> Tensor:
     return out.reshape(shape)
 
 
-def _square_kernel(kernel) -> Tensor:
-    """``kernel`` as a finite fp32 ``(K, K)`` tensor, a rectangular one zero-padded and centred
-    (``psf._square_kernel`` without its size cap)."""
-    k = torch.as_tensor(np.asarray(kernel) if not isinstance(kernel, torch.Tensor) else kernel)
-    k = k.detach().to(device="cpu", dtype=torch.float32)
-    if k.ndim != 2:
-        raise ValueError("kernel must be 2-D (Kh, Kw)")
-    kh, kw = int(k.shape[0]), int(k.shape[1])
-    if kh % 2 != 1 or kw % 2 != 1 or max(kh, kw) < 3:
-        raise ValueError(f"kernel sizes must be odd and the larger at least 3, got {(kh, kw)}")
-    if not bool(torch.isfinite(k).all()):
-        raise ValueError("kernel values must be finite")
-    size = max(kh, kw)
-    out = torch.zeros(size, size, dtype=torch.float32)
-    oy, ox = (size - kh) // 2, (size - kw) // 2
-    out[oy:oy + kh, ox:ox + kw] = k
-    return out
-
-
-def _work(lib, desc, batch: int, like: Tensor) -> Tensor:
-    floats = int(lib.sp_op_workspace(desc, batch))
-    if floats < 0:
-        raise _hip.HipLibraryError(f"sp_op_workspace rejected the descriptor ({floats})")
-    return torch.empty(max(floats, 2), device=like.device, dtype=torch.float32)
-
-
-def _hip_map(op: "FFTPSFBlurOperator", t: Tensor, transpose: bool) -> Tensor:
-    _hip.require_cuda(t, type(op).__name__)
-    if t.dtype != torch.float32:
-        raise _hip.HipLibraryError(f"{type(op).__name__}: HIP operators compute in fp32")
-    lib, desc = _hip.load_library(), op.hip_descriptor()
-    flat, batch = _flatten_batch(t.detach(), op.x_shape)
-    out = torch.empty_like(flat)
-    if flat.shape[0] > 0:
-        work = _work(lib, desc, flat.shape[0], flat)
-        if transpose:  # A^T: the x argument of sp_op_vjp_ws is not read
-            _hip.check(lib.sp_op_vjp_ws(desc, _hip.ptr(flat), _hip.ptr(flat), _hip.ptr(out),
-                                        flat.shape[0], _hip.ptr(work), _hip.stream_of(t)),
-                       "sp_op_vjp_ws")
-        else:
-            _hip.check(lib.sp_op_apply_ws(desc, _hip.ptr(flat), _hip.ptr(out), flat.shape[0],
-                                          _hip.ptr(work), _hip.stream_of(t)), "sp_op_apply_ws")
-    return out.reshape(*batch, *op.x_shape)
-
-
-class HipPSFFFTMap(torch.autograd.Function):
-    """``forward(op, t, transpose)`` is ``sp_op_apply_ws`` (A) or ``sp_op_vjp_ws`` (Aᵀ); the
-    backward of a linear map is the other one, so it differentiates to any order."""
-
-    @staticmethod
-    def forward(ctx, op: "FFTPSFBlurOperator", t: Tensor, transpose: bool) -> Tensor:
-        ctx.op, ctx.transpose = op, transpose
-        return _hip_map(op, t, transpose)
-
-    @staticmethod
-    def backward(ctx, g: Tensor):
-        return None, HipPSFFFTMap.apply(ctx.op, g.to(torch.float32).contiguous(),
-                                        not ctx.transpose), None
-
-
 class FFTPSFBlurOperator(LinearOperator):
     """Depthwise blur by a dense 2-D PSF of any radius below the image size, with reflect,
     circular or zero padding, through FFTs; ``y`` has ``x_shape``."""
@@ -178,33 +115,20 @@ class FFTPSFBlurOperator(LinearOperator):
                  padding: str = "reflect", device: Device = None) -> "FFTPSFBlurOperator":
         """The isotropic Gaussian PSF as the outer product of ``gaussian_taps``, as
         ``PSFBlurOperator.gaussian`` without its size cap."""
-        if sigma <= 0:
-            raise ValueError("sigma must be positive")
-        if kernel_size % 2 != 1 or kernel_size < 3:
-            raise ValueError("kernel_size must be odd and at least 3")
-        t = gaussian_taps(kernel_size, sigma).to(torch.float64)
-        return cls(x_shape, torch.outer(t, t).to(torch.float32), padding=padding, device=device)
+        return cls(x_shape, _gaussian_psf(kernel_size, sigma), padding=padding, device=device)
 
     def apply(self, x: Tensor) -> Tensor:
         if x.is_cuda:
-            return HipPSFFFTMap.apply(self, x, False)
+            return HipWorkspaceMap.apply(self, x, False, False)
         return psf_pad_torch(x, self.kernel, self.padding)
 
     def apply_transpose(self, y: Tensor) -> Tensor:
         if y.is_cuda:
-            return HipPSFFFTMap.apply(self, y, True)
-        x = torch.zeros_like(y, requires_grad=True)
-        with torch.enable_grad():
-            out = psf_pad_torch(x, self.kernel, self.padding)
-            (g,) = torch.autograd.grad(out, x, grad_outputs=y)
-        return g
+            return HipWorkspaceMap.apply(self, y, False, True)
+        return _transpose_by_grad(lambda x: psf_pad_torch(x, self.kernel, self.padding), y)
 
     def hip_descriptor(self) -> _hip.SpOp:
-        c, h, w = self.x_shape
-        d = _hip.SpOp()
-        d.kind = _hip.SP_OP_PSF_FFT
-        d.channels, d.height, d.width = c, h, w
-        d.n = d.m = int(math.prod(self.x_shape))
+        d = _plane_descriptor(_hip.SP_OP_PSF_FFT, self.x_shape)
         d.taps = self.spectrum.data_ptr()
         d.radius = self.radius
         d.factor = PADDINGS.index(self.padding)
