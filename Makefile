@@ -12,7 +12,8 @@ SRC := samplers_amd/csrc/sp_dps.hip samplers_amd/csrc/sp_blur.hip samplers_amd/c
        samplers_amd/csrc/sp_conv_s2.hip samplers_amd/csrc/sp_upsample.hip \
        samplers_amd/csrc/sp_attention.hip samplers_amd/csrc/sp_attention6.hip \
        samplers_amd/csrc/sp_gemm_x6.hip samplers_amd/csrc/sp_transformer.hip \
-       samplers_amd/csrc/sp_bf16.hip
+       samplers_amd/csrc/sp_bf16_conv.hip samplers_amd/csrc/sp_bf16_groupnorm.hip \
+       samplers_amd/csrc/sp_bf16_rows.hip samplers_amd/csrc/sp_bf16_attention.hip
 OBJ := $(patsubst samplers_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB := samplers_amd/lib/libsamplers_hip.so
 # bounds-checked debug build (SP_DCHECK index / range invariants counted on the device,
@@ -31,10 +32,13 @@ build/sp_wino.o build/debug/sp_wino.o: EXTRA := -fno-slp-vectorize
 # by moves (measured no faster at R = 30, 9-12 % slower at R <= 15)
 build/sp_psf.o build/debug/sp_psf.o: EXTRA := -fno-slp-vectorize
 # the attention kernels keep their accumulators in VGPRs: in the AGPR form the compiler copied
-# every score / output block between the two register files around each MFMA
-build/sp_attention.o build/debug/sp_attention.o build/sp_attention6.o build/debug/sp_attention6.o build/sp_bf16.o build/debug/sp_bf16.o: EXTRA := -mllvm -amdgpu-mfma-vgpr-form=1
+# every score / output block between the two register files around each MFMA; the bf16 conv tile
+# was tuned under the same form (sp_bf16_groupnorm and sp_bf16_rows have no MFMA: their device
+# code is the same either way)
+VGPR_FORM := sp_attention sp_attention6 sp_bf16_conv sp_bf16_attention
+$(VGPR_FORM:%=build/%.o) $(VGPR_FORM:%=build/debug/%.o): EXTRA := -mllvm -amdgpu-mfma-vgpr-form=1
 
-build/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h samplers_amd/csrc/sp_fft.h include/samplers_hip.h
+build/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h samplers_amd/csrc/sp_fft.h samplers_amd/csrc/sp_bf16.h include/samplers_hip.h
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) $(EXTRA) -c $< -o $@
 
@@ -42,7 +46,7 @@ $(LIB): $(OBJ)
 	@mkdir -p samplers_amd/lib
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $(OBJ)
 
-build/debug/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h samplers_amd/csrc/sp_fft.h include/samplers_hip.h
+build/debug/%.o: samplers_amd/csrc/%.hip samplers_amd/csrc/sp_common.h samplers_amd/csrc/sp_ops.h samplers_amd/csrc/sp_fft.h samplers_amd/csrc/sp_bf16.h include/samplers_hip.h
 	@mkdir -p build/debug
 	$(HIPCC) $(CXXFLAGS) $(EXTRA) -DSP_DEBUG=1 -c $< -o $@
 

@@ -790,7 +790,7 @@ int sp_conv1x1_small_supported(int32_t cin, int32_t cout, int64_t hw);
 int sp_conv1x1_small(const float* x, const float* w, const float* b, int64_t n, int32_t cin, int32_t cout,
                      int64_t hw, int32_t trans, float* y, sp_stream_t stream);
 
-/* ---- The priors at reduced precision (bf16), NHWC activations (csrc/sp_bf16.hip) ----------
+/* ---- The priors at reduced precision (bf16), NHWC activations (csrc/sp_bf16_*.hip) --------
  * The reference's adapters take any torch_dtype and its PSLD driver runs SD 1.5 in bf16
  * (reference: samplers/networks/diffusers/stable_diffusion.py:90-101, ddpm.py:23-34,
  * scripts/run_psld.py:14-20).  These entry points are the bf16 layers of those priors:

@@ -1,4 +1,4 @@
-"""The bf16 attention kernels (``k_attnb_fwd`` / ``_dq`` / ``_dkv`` of csrc/sp_bf16.hip) where the
+"""The bf16 attention kernels (``k_attnb_fwd`` / ``_dq`` / ``_dkv`` of csrc/sp_bf16_attention.hip) where the
 SD-shaped ``randn`` tests never take them: peaked rows, on which the lazily moved softmax reference
 point moves and live accumulators are rescaled (tests/attn_ref.py; tests/test_attn_ref.py shows on the
 CPU that every ``up`` / ``saw`` case here moves it for every query), and ragged shapes — n, m that

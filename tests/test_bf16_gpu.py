@@ -1,5 +1,5 @@
 """The priors at the reference's reduced precision (bf16) on this project's kernels
-(``csrc/sp_bf16.hip`` through ``networks/bf16.py``).
+(``csrc/sp_bf16_*.hip`` through ``networks/bf16.py``).
 
 The reference runs its priors in whatever ``torch_dtype`` it is given; its PSLD driver uses SD 1.5
 in bf16 (``/root/reference/scripts/run_psld.py:14-20``, ``stable_diffusion.py:90-101``).  What is
