@@ -17,6 +17,7 @@ from .psf import MotionBlurOperator, PSFBlurOperator, motion_blur_kernel
 from .periodic import PeriodicBlurOperator, pseudo_inverse_spectrum, transfer_function
 from .psf_fft import FFTPSFBlurOperator, padded_size, psf_spectrum
 from .radon import RadonOperator, radon_table
+from .sr_filter import BicubicSuperResolutionOperator, FilteredSuperResolutionOperator, bicubic_taps
 from .superres import SuperResolutionOperator
 
 __all__ = [
@@ -33,6 +34,9 @@ __all__ = [
     "RandomInpaintingOperator",
     "GaussianBlurOperator",
     "SuperResolutionOperator",
+    "FilteredSuperResolutionOperator",
+    "BicubicSuperResolutionOperator",
+    "bicubic_taps",
     "PSFBlurOperator",
     "MotionBlurOperator",
     "FFTPSFBlurOperator",
