@@ -1,6 +1,6 @@
 /*
  * samplers_hip.h — C ABI of libsamplers_hip.so, the MI355X (gfx950) hot path of
- * diffusion posterior sampling (DPS / PSLD / PGDM / ReSample guidance steps).
+ * diffusion posterior sampling (DPS / PSLD / PGDM / ReSample / DiffPIR guidance steps).
  *
  * The reference (thomashirtz/samplers) is pure Python over PyTorch; every entry
  * point below replaces a group of eager ATen calls that the reference issues
@@ -24,7 +24,7 @@
  *     point over rows of n (or m) elements chooses float4 access from n % 4 == 0 alone and then
  *     REQUIRES 16-byte aligned row buffers, y included where m == n (rows are n floats apart,
  *     so the base pointer decides): sp_dps_residual / sp_dps_update and their _sched forms, sp_residual_grad (m),
- *     sp_randn, sp_op_apply / sp_op_adjoint, sp_psld_pixel, sp_psld_cotangent,
+ *     sp_randn, sp_op_apply / sp_op_adjoint, sp_op_prox_ws, sp_diffpir_step_ws, sp_psld_pixel, sp_psld_cotangent,
  *     sp_pixel_opt_step, sp_ddim_eps_step, sp_stochastic_resample.  Packed INPAINT observation
  *     rows (m elements) and partial-sum buffers are read by scalar loads and need only 4-byte
  *     alignment.  With n % 4 != 0 all access is scalar and 4-byte alignment suffices.
@@ -388,6 +388,58 @@ int sp_pgdm_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_
 int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const float* q,
                         int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
                         float* work, sp_stream_t stream);
+
+/* ---- DiffPIR / proximal data step (no reference counterpart: Zhu et al. 2023, semantics in
+ * DESIGN.md §3 and tests/prox_ref.py) -------------------------------------------------------
+ * The proximal map of the operator at x0 with weight rho > 0,
+ *   z = argmin_u |y - A u|^2 + rho |u - x0|^2 = (A^T A + rho I)^-1 (A^T y + rho x0),
+ * in closed form for the kinds where it has one (r = y - A x0):
+ *   IDENTITY, INPAINT, MASK (A A^T = I)   z = x0 + A^T r / (1 + rho); unobserved pixels keep x0;
+ *   SR x s (A A^T = I / s^2)              z = x0 + (r replicated over its block) / (1 + rho s^2),
+ *                                         the block mean of x0 in the order of csrc/sp_sr.hip;
+ *   PSF_PERIODIC (A = IFFT2 M FFT2)       Z = (conj(M) Y + rho X0) / (|M|^2 + rho), z = Re IFFT2(Z).
+ * Every other kind: SP_EUNSUPPORTED (after the common argument checks, which answer SP_EINVAL).
+ * The scalars are applied as reciprocals computed once per thread (1 / a, 1 / k, 1 / (1 + rho s^2),
+ * 1 / (|M|^2 + rho)), as sp_dps_update does.  Plain stores, no atomics; every sample is computed
+ * alone, so the bits do not depend on the batch, y_div or the shard. */
+typedef struct sp_prox_coefs {
+    float a;      /* sqrt(alpha_bar[t])                                       */
+    float k;      /* sqrt(1 - alpha_bar[t])                                   */
+    float rho;    /* guidance_weight * max(sigma_n, sigma_min)^2 * alpha_bar[t] / (1 - alpha_bar[t]) */
+    float a_prev; /* sqrt(alpha_bar[t_prev])                                  */
+    float c_eps;  /* sqrt(1 - alpha_bar[t_prev]) * sqrt(1 - zeta)             */
+    float c_xi;   /* sqrt(1 - alpha_bar[t_prev]) * sqrt(zeta)                 */
+} sp_prox_coefs;  /* 24 bytes */
+/* Floats of `work` that sp_op_prox_ws / sp_diffpir_step_ws need for `batch` samples: 0 for the
+ * elementwise kinds and SR, the sp_op_workspace figure for PSF_PERIODIC.  This is the capability
+ * probe: SP_EUNSUPPORTED for a valid kind without a closed-form prox, SP_EINVAL for a rejected
+ * descriptor or batch <= 0. */
+int64_t sp_prox_workspace(const sp_op* op, int64_t batch);
+/* Floats of `q` for `rows` observation rows: 0 but for PSF_PERIODIC,
+ * 2 * rows * channels * (width/2 + 1) * height there.  Codes as sp_prox_workspace. */
+int64_t sp_prox_prepare_size(const sp_op* op, int64_t rows);
+/* q = conj(M) * FFT2(y) / (H W) per observation row, as (re, im) pairs
+ * [row][channels][width/2 + 1][height] (the intermediate's layout): sp_pgdm_prepare's two launches
+ * with the multiplier conj(M).  Once per sampler call.  The kinds whose sp_prox_prepare_size is 0:
+ * SP_OK, nothing launched, q may be NULL. */
+int sp_prox_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_stream_t stream);
+/* z_out = prox(x0; y, rho) for `batch` rows of x0, sample b against observation row b / y_div.
+ * One launch (elementwise kinds, SR: y read, q and work may be NULL) or three (PSF_PERIODIC: row
+ * FFTs of x0 -> work; per column tile z <- (q[b / y_div] + rho z / (H W)) / (|M|^2 + rho) between
+ * the transforms; inverse row FFTs, real part -> z_out; q and work required, y not read).
+ * z_out may alias x0; work and q must not alias any other argument. */
+int sp_op_prox_ws(const sp_op* op, const float* x0, const float* y, const float* q, int64_t batch,
+                  int64_t y_div, float rho, float* z_out, float* work, sp_stream_t stream);
+/* The whole guided DiffPIR step after the network call, in the same launches:
+ *   x0 = (x - k eps) / a,  z = prox(x0; y, rho),  eps_hat = (x - a z) / k,
+ *   x' = a_prev z + (c_eps eps_hat + c_xi xi)
+ * xi: injected standard normals (batch * n) or NULL to draw Philox4x32-10 normals keyed as
+ * sp_dps_update does, (seed, step, sample_offset + b, flat element index).  x_out may alias x.
+ * rho <= 0, a non-finite rho or k == 0: SP_EINVAL. */
+int sp_diffpir_step_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                       const float* q, const float* xi, uint64_t seed, int64_t step,
+                       int64_t sample_offset, int64_t batch, int64_t y_div,
+                       const sp_prox_coefs* coefs, float* x_out, float* work, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
  *   r = y[b/y_div] - z[b];  g[b] = grad_scale * r;  rsq_partial[b][p] += r^2 partials.

@@ -66,6 +66,11 @@ class SpDpsCoefs(ctypes.Structure):
     ]
 
 
+class SpProxCoefs(ctypes.Structure):
+    """Scalars of one DiffPIR step (include/samplers_hip.h sp_prox_coefs), 24 bytes."""
+    _fields_ = [(f, ctypes.c_float) for f in ("a", "k", "rho", "a_prev", "c_eps", "c_xi")]
+
+
 class SpStepRec(ctypes.Structure):
     """One record of the device-resident step schedule (include/samplers_hip.h)."""
     _fields_ = [("c", SpDpsCoefs), ("step", ctypes.c_int64), ("t", ctypes.c_int64)]
@@ -119,6 +124,12 @@ SIGNATURES = {
     "sp_op_pinv_ws": (ctypes.c_int, [_OPP, _P, _P, _I64, ctypes.c_int32, _P, _P]),
     "sp_pgdm_prepare": (ctypes.c_int, [_OPP, _P, _I64, _P, _P]),
     "sp_pgdm_residual_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _COP, _P, _P, _P]),
+    "sp_prox_workspace": (_I64, [_OPP, _I64]),
+    "sp_prox_prepare_size": (_I64, [_OPP, _I64]),
+    "sp_prox_prepare": (ctypes.c_int, [_OPP, _P, _I64, _P, _P]),
+    "sp_op_prox_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _F, _P, _P, _P]),
+    "sp_diffpir_step_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _P, _P, _U64, _I64, _I64, _I64, _I64,
+                                          ctypes.POINTER(SpProxCoefs), _P, _P, _P]),
     "sp_residual_grad": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "sp_psld_pixel": (ctypes.c_int, [_OPP, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "sp_sum_partials": (ctypes.c_int, [_P, _I64, _P, _P]),

@@ -266,6 +266,95 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_dps_update(
 }
 
 // ---------------------------------------------------------------------------
+// K3: the proximal data step of IDENTITY / INPAINT / MASK (A A^T = I), one launch:
+//   z = x0 + A^T (y - A x0) / (1 + rho); unobserved pixels keep x0
+// STEP false (sp_op_prox_ws): x holds x0, z is written.  STEP true (sp_diffpir_step_ws):
+//   x0 = (x - k eps) / a,  eps_hat = (x - a z) / k,  x' = a_prev z + (c_eps eps_hat + c_xi xi)
+// with xi read or drawn as in K2 (flat element index).  The three divisions are multiplications
+// by reciprocals taken once per thread.  Same tiles as K2: a block covers kIter * kBlock * V
+// consecutive elements of one sample, every element is read and written by one thread (the output
+// may alias x).  Bytes per element: 12 + 4 per observed one (x, eps read, x' written, y read); the
+// prox form 8 + 4; the keep words add 12 B per 64 elements.
+// ---------------------------------------------------------------------------
+template <int OPK, int V, bool STEP, bool XI_IN>
+__global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_prox(
+    sp_op op, const float* __restrict__ x, const float* __restrict__ eps,
+    const float* __restrict__ y, const float* __restrict__ xi, uint64_t seed, int64_t step,
+    int64_t sample_offset, int64_t y_div, sp_prox_coefs c, float* __restrict__ out) {
+    const int64_t b = blockIdx.y;
+    const int64_t n = op.n;
+    const float* xb = x + b * n;
+    const float* eb = STEP ? eps + b * n : nullptr;
+    const float* yb = y + (b / y_div) * op.m;
+    float* ob = out + b * n;
+    const int64_t j0 = (int64_t)blockIdx.x * kIter * (kBlock * V) + threadIdx.x * V;
+    float xv[kIter][V], ev[kIter][V], yv[kIter][V];
+    uint32_t bits[kIter];
+    int64_t rank[kIter];
+#pragma unroll
+    for (int it = 0; it < kIter; ++it) {
+        const int64_t j = j0 + it * (kBlock * V);
+        if (j < n) {
+            SP_DCHECK(j + V <= n);
+            load_v<V, SP_UPD_NT>(xb + j, xv[it]);
+            if constexpr (STEP) load_v<V, SP_UPD_NT>(eb + j, ev[it]);
+            if constexpr (OPK == SP_OP_INPAINT) {
+                inpaint_lookup(op, j, bits[it], rank[it]);
+            } else {
+                load_v<V>(yb + j, yv[it]);
+                if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
+            }
+        }
+    }
+    if constexpr (OPK == SP_OP_INPAINT) {
+#pragma unroll
+        for (int it = 0; it < kIter; ++it) {
+            const int64_t j = j0 + it * (kBlock * V);
+            if (j < n) {
+                int64_t r = rank[it];
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    yv[it][e] = 0.f;
+                    if ((bits[it] >> e) & 1u) yv[it][e] = yb[r];
+                    r += (bits[it] >> e) & 1u;
+                }
+                SP_DCHECK(r <= op.m);  // packed observation index inside the row
+            }
+        }
+    }
+    const float inv_d = 1.f / (1.f + c.rho);
+    const float inv_a = STEP ? 1.f / c.a : 1.f, inv_k = STEP ? 1.f / c.k : 1.f;
+#pragma unroll
+    for (int it = 0; it < kIter; ++it) {
+        const int64_t j = j0 + it * (kBlock * V);
+        if (j < n) {
+            float nz[V] = {};
+            if constexpr (STEP) {
+                if constexpr (XI_IN) load_v<V>(xi + b * n + j, nz);
+                else philox_normals<V>(seed, step, sample_offset + b, j, nz);
+            }
+            float o[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+// every product and sum below rounds on its own: the bits are those of the expression as written,
+// whichever noise form the kernel was built for
+#pragma clang fp contract(off)
+                const bool kept = OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+                const float x0 = STEP ? (xv[it][e] - c.k * ev[it][e]) * inv_a : xv[it][e];
+                const float z = kept ? x0 + (yv[it][e] - x0) * inv_d : x0;
+                if constexpr (STEP) {
+                    const float eh = (xv[it][e] - c.a * z) * inv_k;
+                    o[e] = c.a_prev * z + (c.c_eps * eh + c.c_xi * nz[e]);
+                } else {
+                    o[e] = z;
+                }
+            }
+            store_v<V, STEP>(ob + j, o);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // elementwise helpers
 // ---------------------------------------------------------------------------
 template <int V>
@@ -432,11 +521,36 @@ static int elementwise_map(const sp_op* op, const float* in, float* out, int64_t
     return check_launch(what);
 }
 
+// the proximal data step, alone (p.eps null) or inside the DiffPIR step: one launch of K3
+static int elementwise_prox(const sp_op* op, const prox_args& p, hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>(tiles_elementwise(op->n)), static_cast<unsigned>(p.batch));
+    const bool v4 = op->n % 4 == 0;
+#define SP_K3(OPK, V, STEP, XIN)                                                              \
+    launch(0, k_prox<OPK, V, STEP, XIN>, grid, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, \
+           p.step, p.sample_offset, p.y_div, p.c, p.out)
+#define SP_K3_FORM(OPK, V)                                  \
+    if (!p.eps) SP_K3(OPK, V, false, false);                \
+    else if (p.xi) SP_K3(OPK, V, true, true);               \
+    else SP_K3(OPK, V, true, false)
+#define SP_K3_V(OPK) \
+    if (v4) { SP_K3_FORM(OPK, 4); } else { SP_K3_FORM(OPK, 1); }
+    switch (op->kind) {
+        case SP_OP_IDENTITY: SP_K3_V(SP_OP_IDENTITY) break;
+        case SP_OP_MASK: SP_K3_V(SP_OP_MASK) break;
+        default: SP_K3_V(SP_OP_INPAINT) break;
+    }
+#undef SP_K3_V
+#undef SP_K3_FORM
+#undef SP_K3
+    return check_launch(p.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws");
+}
+
 // The dispatch table: one row per kind, indexed by sp_op.kind (sp_ops.h)
 #define SP_ELEMENTWISE_ROW(VALID)                                                              \
     {VALID, elementwise_partials, nullptr, nullptr, elementwise_dps_residual,                  \
      elementwise_map<false>, elementwise_map<true>, nullptr, nullptr, elementwise_psld_pixel,  \
-     elementwise_psld_cotangent, elementwise_pixel_opt, SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR}
+     elementwise_psld_cotangent, elementwise_pixel_opt, SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, \
+     nullptr, nullptr, nullptr, nullptr, nullptr, elementwise_prox, elementwise_prox}
 static const op_kind g_kinds[] = {
     /* SP_OP_IDENTITY */ SP_ELEMENTWISE_ROW(identity_valid),
     /* SP_OP_INPAINT */ SP_ELEMENTWISE_ROW(inpaint_valid),
@@ -448,7 +562,8 @@ static const op_kind g_kinds[] = {
     /* SP_OP_SR */
     {sr_valid, sr_partials, nullptr, nullptr, sr_dps_residual, sr_apply, sr_adjoint, nullptr,
      nullptr, sr_psld_pixel, sr_psld_cotangent, sr_pixel_opt,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR},
+     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, nullptr, nullptr, nullptr,
+     nullptr, nullptr, sr_prox, sr_prox},
     /* SP_OP_PSF: as BLUR, and two launches through the caller's work buffer (_ws forms) */
     {psf_valid, psf_partials, psf_workspace, nullptr, psf_dps_residual, psf_apply, psf_adjoint,
      nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
@@ -463,11 +578,13 @@ static const op_kind g_kinds[] = {
      nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr, nullptr, nullptr,
      SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
     /* SP_OP_PSF_PERIODIC: PSF_FFT's functions on exact-size transforms (nothing extended or
-       folded), and the only kind with the pseudo-inverse columns: A^+, the PGDM pass 1 */
+       folded), and the only kind with the pseudo-inverse columns: A^+, the PGDM pass 1; its
+       proximal map is one more multiplier between the column transforms */
     {psf_periodic_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace,
      psf_fft_dps_residual, nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr,
      nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
-     psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual},
+     psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual,
+     psf_fft_workspace, psf_periodic_prox_prepare, psf_periodic_prox, psf_periodic_prox},
     /* SP_OP_RADON: as PSF (project, then backproject through the caller's work buffer), with an
        observation space of its own geometry: m = channels * radius * factor */
     {radon_valid, radon_partials, radon_workspace, nullptr, radon_dps_residual, radon_apply,
@@ -496,7 +613,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 108; }
+int sp_version(void) { return 109; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -802,6 +919,61 @@ int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const
     if (!k->pgdm_residual) return SP_EUNSUPPORTED;
     return k->pgdm_residual(op, x, eps, q, batch, y_div, *c, v_out, work,
                             static_cast<hipStream_t>(stream));
+}
+
+// ---- DiffPIR / proximal data step ----
+int64_t sp_prox_workspace(const sp_op* op, int64_t batch) {
+    if (!valid_op(op) || batch <= 0) return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->prox) return SP_EUNSUPPORTED;
+    return k->prox_workspace ? k->prox_workspace(op, batch) : 0;
+}
+
+// q has the intermediate's layout, so one row of it is one sample's workspace
+int64_t sp_prox_prepare_size(const sp_op* op, int64_t rows) { return sp_prox_workspace(op, rows); }
+
+int sp_prox_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_stream_t stream) {
+    if (!valid_op(op) || !y || rows <= 0 || rows > 65535) return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->prox) return SP_EUNSUPPORTED;
+    if (!k->prox_prepare) return SP_OK;  // nothing to prepare: the launch reads y itself
+    if (!q) return SP_EINVAL;
+    return k->prox_prepare(op, y, rows, q, static_cast<hipStream_t>(stream));
+}
+
+static bool prox_rho_ok(float rho) { return rho > 0.f && rho <= 3.402823466e+38f; }  // NaN fails both
+
+// the kind's own buffers: y where the launch reads it, q and work where the kind prepares
+static bool prox_buffers_ok(const op_kind* k, const prox_args& p) {
+    return k->prox_prepare ? p.q && p.work : p.y != nullptr;
+}
+
+int sp_op_prox_ws(const sp_op* op, const float* x0, const float* y, const float* q, int64_t batch,
+                  int64_t y_div, float rho, float* z_out, float* work, sp_stream_t stream) {
+    if (!valid_op(op) || !x0 || !z_out || batch <= 0 || y_div <= 0 || batch > 65535 ||
+        !prox_rho_ok(rho))
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->prox) return SP_EUNSUPPORTED;
+    const prox_args p = {x0, nullptr, y, q, nullptr, 0, 0, 0, batch, y_div,
+                         {1.f, 1.f, rho, 0.f, 0.f, 0.f}, z_out, work};
+    if (!prox_buffers_ok(k, p)) return SP_EINVAL;
+    return k->prox(op, p, static_cast<hipStream_t>(stream));
+}
+
+int sp_diffpir_step_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                       const float* q, const float* xi, uint64_t seed, int64_t step,
+                       int64_t sample_offset, int64_t batch, int64_t y_div,
+                       const sp_prox_coefs* coefs, float* x_out, float* work, sp_stream_t stream) {
+    if (!valid_op(op) || !x || !eps || !coefs || !x_out || batch <= 0 || y_div <= 0 ||
+        batch > 65535 || !prox_rho_ok(coefs->rho) || coefs->k == 0.f)
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->diffpir_step) return SP_EUNSUPPORTED;
+    const prox_args p = {x, eps, y, q, xi, seed, step, sample_offset, batch, y_div, *coefs, x_out,
+                         work};
+    if (!prox_buffers_ok(k, p)) return SP_EINVAL;
+    return k->diffpir_step(op, p, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

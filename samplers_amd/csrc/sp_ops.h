@@ -20,6 +20,15 @@ struct dps_residual_args {
     float* work;  // null in the forms without a workspace and where the kind needs none
 };
 
+// sp_op_prox_ws (eps null: x holds x0, out = z) and sp_diffpir_step_ws (eps set: out = x')
+struct prox_args {
+    const float *x, *eps, *y, *q, *xi;  // y: the one-launch kinds; q: the kinds with a prepare
+    uint64_t seed;
+    int64_t step, sample_offset, batch, y_div;
+    sp_prox_coefs c;  // the prox form reads rho alone
+    float *out, *work;
+};
+
 typedef bool valid_fn(const sp_op* op);
 typedef int64_t partials_fn(const sp_op* op);
 typedef int64_t workspace_fn(const sp_op* op, int64_t batch);
@@ -43,6 +52,7 @@ typedef int pgdm_prepare_fn(const sp_op* op, const float* y, int64_t rows, float
 typedef int pgdm_residual_fn(const sp_op* op, const float* x, const float* eps, const float* q,
                              int64_t batch, int64_t y_div, const sp_dps_coefs& c, float* v,
                              float* work, hipStream_t s);
+typedef int prox_fn(const sp_op* op, const prox_args& p, hipStream_t s);
 
 // One row per sp_op kind.  A null member is the library's answer for a kind without that pass:
 // 0 floats of workspace, or SP_EUNSUPPORTED (apply_ws: sp_op_apply).
@@ -63,6 +73,12 @@ struct op_kind {
     pinv_ws_fn* pinv_ws;
     pgdm_prepare_fn* pgdm_prepare;
     pgdm_residual_fn* pgdm_residual;
+    // the kinds with a closed-form proximal map (sp_prox_workspace answers for the others): the
+    // floats of work and of q (null: none, and nothing to prepare), q's two launches, z alone and
+    // the whole DiffPIR step
+    workspace_fn* prox_workspace;
+    pgdm_prepare_fn* prox_prepare;
+    prox_fn *prox, *diffpir_step;
 };
 
 const op_kind* kind_of(const sp_op* op);  // null for an unknown kind or a null op
@@ -90,5 +106,7 @@ pgdm_residual_fn psf_periodic_pgdm_residual;
 psld_pixel_fn elementwise_psld_pixel, sr_psld_pixel;
 psld_cotangent_fn elementwise_psld_cotangent, sr_psld_cotangent;
 pixel_opt_fn elementwise_pixel_opt, sr_pixel_opt;
+pgdm_prepare_fn psf_periodic_prox_prepare;
+prox_fn sr_prox, psf_periodic_prox;  // both forms: p.eps selects (elementwise kinds: sp_dps.hip)
 
 }  // namespace sp

@@ -50,8 +50,18 @@
 namespace sp {
 
 enum { PF_REFLECT = 0, PF_CIRCULAR = 1, PF_ZEROS = 2 };
-enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2 };
-enum { PF_COL_MAP = 0, PF_COL_PREPARE = 1, PF_COL_PGDM = 2 };
+enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2, PF_OUT_PROX = 3 };
+enum { PF_COL_MAP = 0, PF_COL_PREPARE = 1, PF_COL_PGDM = 2, PF_COL_PROX = 3 };
+
+// what the PF_OUT_PROX epilogue of k_pf_rows_inv needs besides z (the other forms pass an empty
+// one): step != 0 forms eps_hat from x and writes the DiffPIR sample, else z itself
+struct pf_prox_tail {
+    const float *x, *xi;
+    uint64_t seed;
+    int64_t step, sample_offset;
+    sp_prox_coefs c;
+    int step_form;
+};
 
 // smallest 2^k or 3 * 2^k in [8, 1024] that is >= n; 0 if there is none
 static int pf_size(int n) {
@@ -147,12 +157,16 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows(pf_geom g, const float* __re
 //   PF_COL_PREPARE  forward transform, times spec / (Nh Nw), stored as the spectrum it is
 //                   (sp_pgdm_prepare: Q = P * FFT2(y));
 //   PF_COL_PGDM     z <- gs (Q[b / y_div] - (spec != 0 ? z / (Nh Nw) : 0)) between the transforms
-//                   (sp_pgdm_residual_ws: spec = P, so spec != 0 is the kept set).
+//                   (sp_pgdm_residual_ws: spec = P, so spec != 0 is the kept set);
+//   PF_COL_PROX     z <- (Q[b / y_div] + rho z / (Nh Nw)) / (|spec|^2 + rho) between the transforms
+//                   (the proximal map: spec = M, Q = conj(M) FFT2(y) / (Nh Nw), gs carries rho).
+// PF_COL_PREPARE with ADJ is the same launch with the multiplier conjugated (sp_prox_prepare).
 template <bool ADJ, bool EXT = true, int FORM = PF_COL_MAP>
 __global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restrict__ ws, int T,
                                                     const float2* __restrict__ qs, int64_t y_div,
                                                     float gs) {
-    static_assert(EXT ? FORM == PF_COL_MAP : (FORM == PF_COL_MAP || !ADJ), "forms of the periodic kind");
+    static_assert(EXT ? FORM == PF_COL_MAP : (FORM == PF_COL_MAP || FORM == PF_COL_PREPARE || !ADJ),
+                  "forms of the periodic kind");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int N = g.Nh, NP = phase_np(N);
     float2* tw = reinterpret_cast<float2*>(smem);
@@ -197,6 +211,18 @@ __global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restric
             const bool kept = p.x != 0.f || p.y != 0.f;
             const float2 pz = kept ? make_float2(s * zp->x, s * zp->y) : make_float2(0.f, 0.f);
             *zp = make_float2(gs * (qv.x - pz.x), gs * (qv.y - pz.y));
+        }
+    } else if constexpr (FORM == PF_COL_PROX) {
+        const int64_t qplane = ((int64_t)blockIdx.y / y_div) * g.C + c;
+        const float2* __restrict__ qp = qs + (qplane * g.HW + kw0) * (int64_t)N;
+        const float rs = gs * s;  // rho / (Nh Nw)
+        for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int t = idx / N, kh = idx - t * N;
+            SP_DCHECK(t < lines && kw0 + t < g.HW && kh < g.H);
+            const float2 m = hsp[idx], qv = qp[idx];
+            float2* zp = z + t * NP + phase_slot(kh);
+            const float inv = 1.f / ((m.x * m.x + m.y * m.y) + gs);
+            *zp = make_float2((qv.x + rs * zp->x) * inv, (qv.y + rs * zp->y) * inv);
         }
     } else {
         constexpr bool CONJ = EXT ? !ADJ : ADJ;
@@ -246,7 +272,8 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
                                                         const float* __restrict__ y, int64_t y_div,
                                                         float gs, float* __restrict__ partial, int P,
                                                         int T, const sp_step_rec* __restrict__ sched,
-                                                        const int32_t* __restrict__ cursor) {
+                                                        const int32_t* __restrict__ cursor,
+                                                        pf_prox_tail px) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ float red[4];
     if (OUT == PF_OUT_RESIDUAL && sched) gs = sched[*cursor].c.grad_scale;
@@ -309,6 +336,38 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
                 SP_DCHECK(kw < g.HW && kw * g.H + h < g.HW * g.H);
                 wp[kw * g.H + h] = f[t * NP + phase_slot(kw)];
             }
+        }
+    } else if constexpr (OUT == PF_OUT_PROX) {
+        // z = the real part; four columns per thread (W % 4 == 0 for every transform length), so
+        // x, xi and the output move as float4 and one Philox draw serves its four elements
+        float* __restrict__ op_out = out + plane * g.H * g.W;
+        const float* __restrict__ xp = px.step_form ? px.x + plane * g.H * g.W : nullptr;
+        const float* __restrict__ nzp = px.xi ? px.xi + plane * g.H * g.W : nullptr;
+        const float inv_k = px.step_form ? 1.f / px.c.k : 1.f;
+        const int groups = g.W / 4;
+        SP_DCHECK(g.W % 4 == 0 && N == g.W);
+        for (int idx = threadIdx.x; idx < T * groups; idx += kBlock) {
+            const int t = idx / groups, j = (idx - t * groups) * 4, h = h0 + t;
+            if (h >= g.H) continue;
+            SP_DCHECK(h * g.W + j + 4 <= g.H * g.W);
+            const float2* rl = res + t * NP;
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = rl[phase_slot(j + e)].x;
+            if (px.step_form) {
+                const int64_t el = (int64_t)c * g.H * g.W + h * g.W + j;  // flat element index
+                float xv[4], nz[4];
+                load_v<4>(xp + h * g.W + j, xv);
+                if (nzp) load_v<4>(nzp + h * g.W + j, nz);
+                else philox_normals<4>(px.seed, px.step, px.sample_offset + b, el, nz);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma clang fp contract(off)  // the bits of the expression as written, in both noise forms
+                    const float eh = (xv[e] - px.c.a * o[e]) * inv_k;
+                    o[e] = px.c.a_prev * o[e] + (px.c.c_eps * eh + px.c.c_xi * nz[e]);
+                }
+            }
+            store_v<4>(op_out + h * g.W + j, o);
         }
     } else {
         float* __restrict__ op_out = out + plane * g.H * g.W;
@@ -449,8 +508,10 @@ static int pf_rows(const pf_run& p, bool adj, const float* in, const pf_x0* x0 =
 static int pf_cols(const pf_run& p, bool adj, int form = PF_COL_MAP, const float2* qs = nullptr,
                    int64_t y_div = 1, float gs = 0.f) {
     const pf_geom& g = p.g;
-    const auto kern = form == PF_COL_PREPARE ? k_pf_cols<false, false, PF_COL_PREPARE>
+    const auto kern = form == PF_COL_PREPARE ? (adj ? k_pf_cols<true, false, PF_COL_PREPARE>
+                                                    : k_pf_cols<false, false, PF_COL_PREPARE>)
                       : form == PF_COL_PGDM  ? k_pf_cols<false, false, PF_COL_PGDM>
+                      : form == PF_COL_PROX  ? k_pf_cols<false, false, PF_COL_PROX>
                       : p.ext                ? (adj ? k_pf_cols<true> : k_pf_cols<false>)
                                              : (adj ? k_pf_cols<true, false> : k_pf_cols<false, false>);
     return fft_stage(p.what, p.kind, 0.0, kern, g.C * pf_col_tiles(g), p.batch, g.Nh, p.s, g, p.ws,
@@ -462,7 +523,16 @@ static int pf_rows_inv(const pf_run& p, bool adj, float* out) {
     const pf_geom& g = p.g;
     const auto kern = adj && p.ext ? k_pf_rows_inv<PF_OUT_AT> : k_pf_rows_inv<PF_OUT_A>;
     return fft_stage(p.what, p.kind, 0.0, kern, g.C * pf_row_tiles(g), p.batch, g.Nw, p.s, g, p.ws,
-                     out, kNoIn, (int64_t)1, 0.f, kNoOut, 0, phase_lines(g.Nw), kNoSched, kNoCursor);
+                     out, kNoIn, (int64_t)1, 0.f, kNoOut, 0, phase_lines(g.Nw), kNoSched, kNoCursor,
+                     pf_prox_tail{});
+}
+
+// launch 3 of the proximal map: ws -> z, or the DiffPIR sample formed from z in the epilogue
+static int pf_rows_prox(const pf_run& p, float* out, const pf_prox_tail& px) {
+    const pf_geom& g = p.g;
+    return fft_stage(p.what, p.kind, 0.0, k_pf_rows_inv<PF_OUT_PROX>, g.C * pf_row_tiles(g), p.batch,
+                     g.Nw, p.s, g, p.ws, out, kNoIn, (int64_t)1, 0.f, kNoOut, 0, phase_lines(g.Nw),
+                     kNoSched, kNoCursor, px);
 }
 
 // the fused launch 3 + 1 of DPS pass 1: ws, r.y -> ws, r.partial
@@ -471,7 +541,7 @@ static int pf_rows_residual(const pf_run& p, const dps_residual_args& r) {
     const int P = g.C * pf_row_tiles(g);
     return fft_stage(p.what, p.kind, 0.0, k_pf_rows_inv<PF_OUT_RESIDUAL>, P, p.batch, g.Nw, p.s, g,
                      p.ws, kNoOut, r.y, r.y_div, r.gs, r.partial, P, phase_lines(g.Nw), r.sched,
-                     r.cursor);
+                     r.cursor, pf_prox_tail{});
 }
 
 // rows, columns, rows^-1 of the map with p's spectrum or of its transpose (adj): in -> ws -> out
@@ -535,6 +605,29 @@ int psf_periodic_pgdm_residual(const sp_op* op, const float* x, const float* eps
     if (rc == SP_OK)
         rc = pf_cols(p, false, PF_COL_PGDM, reinterpret_cast<const float2*>(q), y_div, c.grad_scale);
     if (rc == SP_OK) rc = pf_rows_inv(p, false, v);
+    return rc;
+}
+
+// Q = conj(M) * FFT2(y) / (H W): sp_pgdm_prepare's two launches with the map's own multiplier
+// conjugated (the column launch of A^T that stops at the spectrum)
+int psf_periodic_prox_prepare(const sp_op* op, const float* y, int64_t rows_y, float* q,
+                              hipStream_t s) {
+    const pf_run p = pf_begin("sp_prox_prepare", 0, op, PP_SPEC_M, rows_y, q, s);
+    const int rc = pf_rows(p, false, y);
+    return rc == SP_OK ? pf_cols(p, true, PF_COL_PREPARE) : rc;
+}
+
+// z = Re IFFT2((Q + rho X0) / (|M|^2 + rho)): rows (x0, or x and eps -> work), columns
+// (PF_COL_PROX between the transforms), rows^-1 with the prox epilogue (work -> z or x')
+int psf_periodic_prox(const sp_op* op, const prox_args& a, hipStream_t s) {
+    const pf_run p = pf_begin(a.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws", 0, op, PP_SPEC_M,
+                              a.batch, a.work, s);
+    const pf_x0 x0 = {a.eps, a.c.a, a.c.k, kNoSched, kNoCursor};
+    int rc = pf_rows(p, false, a.x, a.eps ? &x0 : nullptr);
+    if (rc == SP_OK)
+        rc = pf_cols(p, false, PF_COL_PROX, reinterpret_cast<const float2*>(a.q), a.y_div, a.c.rho);
+    if (rc == SP_OK)
+        rc = pf_rows_prox(p, a.out, {a.x, a.xi, a.seed, a.step, a.sample_offset, a.c, a.eps != nullptr});
     return rc;
 }
 

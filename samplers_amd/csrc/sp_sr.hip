@@ -364,6 +364,89 @@ __global__ __launch_bounds__(kBlock) void k_sr_pixel_opt(sp_op op, float* __rest
     if (threadIdx.x == 0) partial[b * P + blockIdx.x] = t;
 }
 
+// The proximal data step (A A^T = I / s^2): z = x0 + (r replicated over its block) / (1 + rho s^2)
+// with r = y - (block mean of x0, summed in the file comment's order).  STEP false
+// (sp_op_prox_ws): x holds x0, z is written.  STEP true (sp_diffpir_step_ws):
+//   x0 = (x - k eps) / a,  eps_hat = (x - a z) / k,  x' = a_prev z + (c_eps eps_hat + c_xi xi)
+// xi read, or drawn by Philox at the flat element index of every patch row (XI_IN false).  The
+// divisions are multiplications by reciprocals taken once per thread; rho s^2 is exact.  A patch
+// is read and written by its own lane alone, so the output may alias x.
+template <int S, int PW, bool STEP, bool XI_IN>
+__global__ __launch_bounds__(kBlock) void k_sr_prox(sp_op op, const float* __restrict__ x,
+                                                    const float* __restrict__ eps,
+                                                    const float* __restrict__ y,
+                                                    const float* __restrict__ xi, uint64_t seed,
+                                                    int64_t step, int64_t sample_offset,
+                                                    int64_t y_div, sp_prox_coefs c,
+                                                    float* __restrict__ out) {
+    using cfg = sr_cfg<S, PW>;
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+    const float* yb = y + (b / y_div) * op.m;
+    const float inv_d = 1.f / (1.f + c.rho * static_cast<float>(S * S));
+    const float inv_a = STEP ? 1.f / c.a : 1.f, inv_k = STEP ? 1.f / c.k : 1.f;
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;  // pairs are in or out together (T and the tile base are even)
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        float xv[S][PW] = {}, zv[S][PW] = {}, yv[cfg::NY] = {};
+        if (in) {
+            sr_load<S, PW, true>(x + b * op.n, pt.xo, op.width, xv);
+            if constexpr (STEP) sr_load<S, PW, true>(eps + b * op.n, pt.xo, op.width, zv);
+            sr_load_y<cfg::NY>(yb, pt.yo, yv);
+        }
+        // every product and sum of the step rounds on its own (no contraction): the bits are those
+        // of the expressions as written, whichever noise form the kernel was built for
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int e = 0; e < PW; ++e) {
+#pragma clang fp contract(off)
+                zv[i][e] = STEP ? (xv[i][e] - c.k * zv[i][e]) * inv_a : xv[i][e];  // x0
+            }
+        float s[cfg::NY], d[cfg::NY];
+        sr_block_sums<S, PW>(zv, s);  // every lane of the wave: S = 8 exchanges half sums
+#pragma unroll
+        for (int j = 0; j < cfg::NY; ++j) {
+#pragma clang fp contract(off)
+            d[j] = (yv[j] - s[j] * cfg::kInv) * inv_d;
+        }
+        if (!in) continue;
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            float nz[PW] = {};
+            if constexpr (STEP) {
+                const int64_t j = pt.xo + (int64_t)i * op.width;  // flat element index of the row
+                if constexpr (XI_IN) {
+                    if constexpr (PW == 4) load_v<4>(xi + b * op.n + j, nz);
+                    else nz[0] = xi[b * op.n + j], nz[1] = xi[b * op.n + j + 1];
+                } else if constexpr (PW == 4) {
+                    SP_DCHECK(j % 4 == 0);
+                    philox_normals<4>(seed, step, sample_offset + b, j, nz);
+                } else {
+                    float q1[1];
+                    philox_normals<1>(seed, step, sample_offset + b, j, q1);
+                    nz[0] = q1[0];
+                    philox_normals<1>(seed, step, sample_offset + b, j + 1, q1);
+                    nz[1] = q1[0];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < PW; ++e) {
+#pragma clang fp contract(off)
+                const float z = zv[i][e] + d[sr_pixel_of<S, PW>(e)];
+                if constexpr (STEP) {
+                    const float eh = (xv[i][e] - c.a * z) * inv_k;
+                    zv[i][e] = c.a_prev * z + (c.c_eps * eh + c.c_xi * nz[e]);
+                } else {
+                    zv[i][e] = z;
+                }
+            }
+        }
+        sr_store<S, PW>(out + b * op.n, pt.xo, op.width, zv);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host side (called from the entry points in sp_dps.hip / sp_latent.hip; `op` is valid)
 // ---------------------------------------------------------------------------
@@ -443,6 +526,30 @@ int sr_pixel_opt(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq, c
     const int P = static_cast<int>(sr_partials(op));
     SR_LAUNCH(0, 0.0, k_sr_pixel_opt, *op, x, exp_avg, exp_avg_sq, y, y_div, gs, *c, stop, partial, P);
     return check_launch("sp_pixel_opt_step");
+}
+
+// one launch over the blocks, alone (p.eps null) or inside the DiffPIR step (xi read or drawn)
+template <bool STEP, bool XI_IN>
+static void sr_prox_launch(const sp_op* op, const prox_args& p, hipStream_t s) {
+    const int64_t batch = p.batch;
+#define SR_PROX(S, PW) k_sr_prox<S, PW, STEP, XI_IN>
+    const dim3 grid_(static_cast<unsigned>(sr_partials(op)), static_cast<unsigned>(batch));
+#define SR_PROX_GO(S, PW)                                                                      \
+    launch(0, SR_PROX(S, PW), grid_, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, p.step, \
+           p.sample_offset, p.y_div, p.c, p.out)
+    if (!sr_vec(op)) SR_PROX_GO(2, 2);
+    else if (op->factor == 2) SR_PROX_GO(2, 4);
+    else if (op->factor == 4) SR_PROX_GO(4, 4);
+    else SR_PROX_GO(8, 4);
+#undef SR_PROX_GO
+#undef SR_PROX
+}
+
+int sr_prox(const sp_op* op, const prox_args& p, hipStream_t s) {
+    if (!p.eps) sr_prox_launch<false, false>(op, p, s);
+    else if (p.xi) sr_prox_launch<true, true>(op, p, s);
+    else sr_prox_launch<true, false>(op, p, s);
+    return check_launch(p.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws");
 }
 
 #undef SR_LAUNCH

@@ -61,6 +61,13 @@ class Operator(torch.nn.Module, ABC):
     def apply_pseudo_inverse(self, y: Tensor) -> Tensor:
         raise NotImplementedError("Pseudo-inverse not defined for this operator")
 
+    def apply_prox(self, x0: Tensor, y: Tensor, rho: float) -> Tensor:
+        """The proximal map of the data term, ``argmin_u ‖y − A u‖² + ρ ‖u − x0‖²`` =
+        ``(AᵀA + ρI)⁻¹(Aᵀy + ρ x0)`` for ``ρ > 0`` (DiffPIR's data step, HQS / plug-and-play).
+        Only the operators with a closed form implement it."""
+        raise NotImplementedError(f"{type(self).__name__} has no closed-form proximal map "
+                                  "(apply_prox)")
+
     def forward(self, x: Tensor) -> Tensor:
         return self.apply(x)
 
@@ -165,6 +172,47 @@ def _hip_workspace_map(op: Operator, t: Tensor, pinv: bool, transpose: bool) -> 
         else:
             _hip.check(lib.sp_op_apply_ws(desc, _hip.ptr(flat), _hip.ptr(out), n, _hip.ptr(work),
                                           stream), "sp_op_apply_ws")
+    return out.reshape(*batch, *op.x_shape)
+
+
+def check_rho(rho: float) -> float:
+    rho = float(rho)
+    if not (rho > 0.0 and math.isfinite(rho)):
+        raise ValueError(f"rho must be positive and finite, got {rho}")
+    return rho
+
+
+def _isometry_prox(op: Operator, x0: Tensor, y: Tensor, rho: float, gram: float = 1.0) -> Tensor:
+    """Host closed form for ``A Aᵀ = gram · I``: ``z = x0 + Aᵀ(y − A x0) / (gram + ρ)``."""
+    return x0 + op.apply_transpose(y - op.apply(x0)) / (gram + check_rho(rho))
+
+
+def _hip_prox(op: Operator, x0: Tensor, y: Tensor, rho: float) -> Tensor:
+    """``sp_op_prox_ws`` on device tensors: ``x0`` of shape ``(*batch, *x_shape)``, one row of
+    ``y`` per sample.  The kinds that prepare (the periodic blur) transform ``y`` first."""
+    rho = check_rho(rho)
+    _hip.require_cuda(x0, type(op).__name__)
+    _hip.require_cuda(y, type(op).__name__)
+    if x0.dtype != torch.float32 or y.dtype != torch.float32:
+        raise _hip.HipLibraryError(f"{type(op).__name__}: HIP operators compute in fp32")
+    lib, desc = _hip.load_library(), op.hip_descriptor()
+    flat, batch = _flatten_batch(x0.detach(), op.x_shape)
+    rows, y_batch = _flatten_batch(y.detach(), op.y_shape)
+    if y_batch != batch:
+        raise ValueError(f"x0 and y must share their batch dimensions, got {batch} and {y_batch}")
+    out = torch.empty_like(flat)
+    n = flat.shape[0]
+    if n > 0:
+        stream = _hip.stream_of(x0)
+        floats, qsize = int(lib.sp_prox_workspace(desc, n)), int(lib.sp_prox_prepare_size(desc, n))
+        if floats < 0 or qsize < 0:
+            raise _hip.HipLibraryError(f"sp_prox_workspace rejected the descriptor ({floats})")
+        work = torch.empty(floats, device=flat.device, dtype=torch.float32) if floats else None
+        q = torch.empty(qsize, device=flat.device, dtype=torch.float32) if qsize else None
+        _hip.check(lib.sp_prox_prepare(desc, _hip.ptr(rows), n, _hip.ptr(q), stream),
+                   "sp_prox_prepare")
+        _hip.check(lib.sp_op_prox_ws(desc, _hip.ptr(flat), _hip.ptr(rows), _hip.ptr(q), n, 1, rho,
+                                     _hip.ptr(out), _hip.ptr(work), stream), "sp_op_prox_ws")
     return out.reshape(*batch, *op.x_shape)
 
 

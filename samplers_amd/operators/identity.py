@@ -7,6 +7,7 @@ import math
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
+from .base import _hip_prox, _isometry_prox
 from .linear import LinearOperator
 
 
@@ -35,6 +36,12 @@ class IdentityOperator(LinearOperator):
         return y
 
     apply_pseudo_inverse = apply_transpose
+
+    def apply_prox(self, x0: Tensor, y: Tensor, rho: float) -> Tensor:
+        """``z = x0 + (y − x0) / (1 + ρ)`` (A Aᵀ = I); ``sp_op_prox_ws`` on device tensors."""
+        if x0.is_cuda:
+            return _hip_prox(self, x0, y, rho)
+        return _isometry_prox(self, x0, y, rho)
 
     def hip_descriptor(self) -> _hip.SpOp:
         n = int(math.prod(self.x_shape))

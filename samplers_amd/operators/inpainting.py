@@ -23,7 +23,7 @@ import torch
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import HipLinearMap
+from .base import HipLinearMap, _hip_prox, _isometry_prox
 from .linear import SVDOperator
 
 
@@ -101,6 +101,13 @@ class InpaintingOperator(SVDOperator):
         return y.masked_fill(self._batch_mask(y), 0)
 
     apply_pseudo_inverse = apply_transpose
+
+    def apply_prox(self, x0: Tensor, y: Tensor, rho: float) -> Tensor:
+        """``z = x0 + Aᵀ(y − A x0) / (1 + ρ)`` (A Aᵀ = I on the kept pixels): the observed pixels
+        move towards ``y``, the masked ones keep ``x0``; ``sp_op_prox_ws`` on device tensors."""
+        if x0.is_cuda:
+            return _hip_prox(self, x0, y, rho)
+        return _isometry_prox(self, x0, y, rho)
 
     def _batch_mask(self, t: Tensor) -> Tensor:
         batch_dims = t.shape[: -len(self._x_shape_internal)]

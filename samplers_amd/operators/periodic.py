@@ -36,8 +36,8 @@ import torch
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import (MAX_SIZE, MIN_SIZE, HipWorkspaceMap, _plane_descriptor, _transpose_by_grad,
-                   transform_size_ok)
+from .base import (MAX_SIZE, MIN_SIZE, HipWorkspaceMap, _hip_prox, _plane_descriptor,
+                   _transpose_by_grad, check_rho, transform_size_ok)
 from .linear import LinearOperator
 from .psf import _gaussian_psf, _square_kernel
 from .psf_fft import psf_pad_torch
@@ -148,6 +148,20 @@ class PeriodicBlurOperator(LinearOperator):
         p = torch.view_as_complex(self.spectra[1]).transpose(0, 1)  # (H, W // 2 + 1)
         cdtype = torch.complex128 if y.dtype == torch.float64 else torch.complex64
         return torch.fft.irfft2(torch.fft.rfft2(y) * p.to(cdtype), s=(h, w)).to(y.dtype)
+
+    def apply_prox(self, x0: Tensor, y: Tensor, rho: float) -> Tensor:
+        """``Z = (conj(M)·Y + ρ·X0) / (|M|² + ρ)``, ``z = Re ifft2(Z)``: the blur is diagonal in the
+        transform, so its proximal map is a per-frequency division (every frequency, not only the
+        kept ones: ρ regularises the small |M|).  ``sp_op_prox_ws`` on device tensors,
+        ``torch.fft`` with the stored M on host tensors."""
+        if x0.is_cuda:
+            return _hip_prox(self, x0, y, rho)
+        rho = check_rho(rho)
+        _, h, w = self.x_shape
+        cdtype = torch.complex128 if x0.dtype == torch.float64 else torch.complex64
+        m = torch.view_as_complex(self.spectra[0]).transpose(0, 1).to(cdtype)  # (H, W // 2 + 1)
+        zs = (m.conj() * torch.fft.rfft2(y.to(x0.dtype)) + rho * torch.fft.rfft2(x0)) / (m.abs() ** 2 + rho)
+        return torch.fft.irfft2(zs, s=(h, w)).to(x0.dtype)
 
     def hip_descriptor(self) -> _hip.SpOp:
         d = _plane_descriptor(_hip.SP_OP_PSF_PERIODIC, self.x_shape)

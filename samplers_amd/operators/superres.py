@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from samplers_amd import _hip
 from samplers_amd.dtypes import Device, Shape, Tensor
 
-from .base import HipLinearMap
+from .base import HipLinearMap, _hip_prox, _isometry_prox
 from .linear import LinearOperator
 
 FACTORS = (2, 4, 8)
@@ -74,6 +74,13 @@ class SuperResolutionOperator(LinearOperator):
         if y.is_cuda:  # s² · Aᵀ y (exact scaling), differentiable like the adjoint
             return HipLinearMap.apply(self, y, True) * float(self.factor * self.factor)
         return self._replicate(y)
+
+    def apply_prox(self, x0: Tensor, y: Tensor, rho: float) -> Tensor:
+        """``z = x0 + (y − A x0 replicated over its block) / (1 + ρ s²)`` (A Aᵀ = I / s²);
+        ``sp_op_prox_ws`` on device tensors."""
+        if x0.is_cuda:
+            return _hip_prox(self, x0, y, rho)
+        return _isometry_prox(self, x0, y, rho, gram=1.0 / float(self.factor * self.factor))
 
     def hip_descriptor(self) -> _hip.SpOp:
         c, h, w = self.x_shape

@@ -1,0 +1,204 @@
+"""DiffPIR: denoising diffusion models for plug-and-play image restoration (Zhu et al., 2023).
+
+The reference has no such sampler; the semantics are this project's own, stated in DESIGN.md §3
+and in fp64 by ``tests/prox_ref.py``.  The loop is ``PGDMSampler``'s (``i = len(ts)−1 … 2``,
+``t = ts[i]``, ``t_prev = ts[i−1]``, the Philox step index is ``i``, the result is
+``predict_x0(x, ts[1])``); one step is::
+
+    eps = unet(x, t)                                      the prior, under no_grad: no VJP
+    x  <- sp_diffpir_step_ws(x, eps, y | q, noise)        HIP: x0, the proximal data step, the update
+
+with ``x0 = (x − k·eps)/a``, ``z = argmin_u ‖y − A u‖² + ρ_t ‖u − x0‖²`` in closed form,
+``eps_hat = (x − a·z)/k`` and ``x' = a_prev·z + k_prev·(sqrt(1−ζ)·eps_hat + sqrt(ζ)·ξ)``, where
+``ρ_t = λ · max(σ_n, σ_min)² · ᾱ_t / (1 − ᾱ_t)``.  The network is called once per step and never
+differentiated, which is where the step's time goes in DPS and PGDM.
+
+Only the operators whose proximal map has a closed form run (``Operator.apply_prox``: identity,
+inpainting / mask, ×s super-resolution, periodic blur); the others raise ``NotImplementedError``.
+The noise model must be ``GaussianNoise``: σ_n enters ρ_t.  The step runs eagerly (no graph
+replay form).  Noise sources (``rng`` / ``seed`` / ``noise_fn``) are ``DPSSampler``'s.
+"""
+
+from __future__ import annotations
+
+from typing import Generic, TypeVar
+
+import torch
+from torch import Tensor
+
+from samplers_amd import _hip
+from samplers_amd.dtypes import Shape
+from samplers_amd.inverse_problem import InverseProblem
+from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod, host_timesteps
+from samplers_amd.noise import GaussianNoise
+from samplers_amd.samplers.base import PosteriorSampler
+from samplers_amd.samplers.dps import (FusedDPSStep, KernelTimer, NoiseFn, draw_seed,
+                                       initial_sample)
+from samplers_amd.samplers.utils.batch_view import BatchView
+from samplers_amd.samplers.utils.bridge_kernels import diffpir_coefficients
+
+Condition_co = TypeVar("Condition_co", covariant=True)
+
+
+def prox_descriptor(operator) -> "_hip.SpOp":
+    """The operator's HIP descriptor if the library has a proximal map for its kind
+    (``sp_prox_workspace`` is the probe; it answers on the host), else ``NotImplementedError``
+    naming the operator."""
+    desc = getattr(operator, "hip_descriptor", lambda: None)()
+    if desc is None or int(_hip.load_library().sp_prox_workspace(desc, 1)) < 0:
+        raise NotImplementedError(
+            f"{type(operator).__name__} has no closed-form proximal map (apply_prox): DiffPIR "
+            "supports IdentityOperator, InpaintingOperator (and subclasses), "
+            "SuperResolutionOperator and PeriodicBlurOperator")
+    return desc
+
+
+class FusedDiffPIRStep:
+    """One DiffPIR iteration over a flat batch: the prior's forward under ``no_grad`` and
+    ``sp_diffpir_step_ws``.  Owns what is fixed across the steps: ``q`` (the prepared observation
+    of the kinds that transform it, once per call), the workspace of a chunk and the micro-batch
+    chunks.  ``observation_rows`` as ``FusedDPSStep``."""
+
+    def __init__(self, network: EpsilonNetwork, inverse_problem: InverseProblem,
+                 observation_rows: Tensor, y_div: int, *, guidance_weight: float = 7.0,
+                 zeta: float = 0.3, min_noise_std: float = 1e-3, micro_batch: int | None = None,
+                 timer: KernelTimer | None = None) -> None:
+        op, noise = inverse_problem.operator, inverse_problem.noise
+        if not isinstance(noise, GaussianNoise):
+            raise ValueError(f"DiffPIR needs GaussianNoise (its sigma sets rho), got "
+                             f"{type(noise).__name__}")
+        self.sigma = float(noise.sigma.detach().cpu().item())
+        self.guidance_weight, self.zeta = float(guidance_weight), float(zeta)
+        self.min_noise_std = float(min_noise_std)
+        if not 0.0 <= self.zeta <= 1.0:
+            raise ValueError(f"zeta must be in [0, 1], got {zeta}")
+        if not self.guidance_weight > 0.0:
+            raise ValueError(f"guidance_weight must be positive, got {guidance_weight}")
+        self.desc = prox_descriptor(op)
+        _hip.require_cuda(observation_rows, "DiffPIRSampler")
+        if observation_rows.dtype != torch.float32:
+            raise TypeError("the HIP path computes in fp32; cast the observation to float32")
+        self.lib = lib = _hip.load_library()
+        self.network, self.operator = network, op
+        self.y = observation_rows.contiguous()
+        self.y_div = int(y_div)
+        self.micro_batch, self.timer = micro_batch, timer
+        self._work: Tensor | None = None
+        rows = self.y.shape[0]
+        qsize = int(lib.sp_prox_prepare_size(self.desc, rows))
+        if qsize < 0:
+            raise _hip.HipLibraryError(f"sp_prox_prepare_size rejected the descriptor ({qsize})")
+        self.q = None
+        if qsize:
+            self.q = torch.empty((rows, qsize // rows), device=self.y.device, dtype=torch.float32)
+            _hip.check(lib.sp_prox_prepare(self.desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
+                                           _hip.stream_of(self.y)), "sp_prox_prepare")
+
+    _chunks = FusedDPSStep._chunks
+    predict_x0 = FusedDPSStep.predict_x0
+
+    def coefficients(self, t: int, t_prev: int) -> _hip.SpProxCoefs:
+        c = diffpir_coefficients(host_alphas_cumprod(self.network), t, t_prev, self.sigma,
+                                 self.guidance_weight, self.zeta, self.min_noise_std)
+        return _hip.SpProxCoefs(c.a, c.k, c.rho, c.a_prev, c.c_eps, c.c_xi)
+
+    def workspace(self, batch: int, like: Tensor) -> Tensor | None:
+        """The step's work buffer for ``batch`` samples (``sp_prox_workspace`` floats), kept
+        between steps; None where the kind needs none."""
+        if self.q is None:
+            return None
+        floats = int(self.lib.sp_prox_workspace(self.desc, batch))
+        if floats < 0:
+            raise _hip.HipLibraryError(f"sp_prox_workspace rejected the descriptor ({floats})")
+        if self._work is None or self._work.numel() < floats or self._work.device != like.device:
+            self._work = torch.empty(floats, device=like.device, dtype=torch.float32)
+        return self._work
+
+    def __call__(self, x: Tensor, step: int, t: int, t_prev: int, *, xi: Tensor | None = None,
+                 seed: int = 0, sample_offset: int = 0) -> Tensor:
+        """Advance ``x`` (flat ``(B, *x_shape)``, contiguous fp32) one step, in place."""
+        coefs = self.coefficients(t, t_prev)
+        stream = _hip.stream_of(x)
+        for b0, b1 in self._chunks(x.shape[0]):
+            xc, bc, row = x[b0:b1], b1 - b0, b0 // self.y_div
+            with torch.no_grad():
+                eps = self.network.forward(xc, t)
+            eps = eps.contiguous()
+            xic = None if xi is None else xi[b0:b1].contiguous()
+            span = self.timer.span("diffpir_step", bc) if self.timer else None
+            if span:
+                span.__enter__()
+            _hip.check(self.lib.sp_diffpir_step_ws(
+                self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
+                _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed, step,
+                sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
+                _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_ws")
+            if span:
+                span.__exit__(None, None, None)
+        return x
+
+
+class DiffPIRSampler(PosteriorSampler, Generic[Condition_co]):
+    """DiffPIR (Zhu et al., 2023): one network call per step, the data step a closed-form
+    proximal map fused with the update into the operator's HIP launches."""
+
+    def __call__(
+        self,
+        inverse_problem: InverseProblem,
+        num_sampling_steps: int = 100,
+        num_reconstructions: int = 1,
+        guidance_weight: float = 7.0,
+        zeta: float = 0.3,
+        min_noise_std: float = 1e-3,
+        condition: Condition_co | None = None,
+        keep_reconstruction_dim: bool = False,
+        *args,
+        rng: str = "philox",
+        seed: int | None = None,
+        noise_fn: NoiseFn | None = None,
+        sample_offset: int = 0,
+        micro_batch: int | None = None,
+        timer: KernelTimer | None = None,
+        **kwargs,
+    ) -> Tensor:
+        """Run DiffPIR; returns ``(*batch_shape, R, *x_shape)`` (R squeezed when 1).
+        ``guidance_weight`` is λ, ``zeta`` the share of fresh noise in a step, ``min_noise_std``
+        the floor of σ_n inside ρ_t; the keyword-only options are ``PGDMSampler``'s."""
+        if args or kwargs:
+            print(f"Warning: Unused args={args}, kwargs={kwargs} in DiffPIRSampler")
+        operator = inverse_problem.operator
+        x_shape: Shape = operator.x_shape
+        batch_shape: Shape = inverse_problem.batch_shape
+        view = BatchView(batch_shape=batch_shape, num_samples=num_reconstructions, data_shape=x_shape)
+        net = self._network
+        net.set_sampling_parameters(num_sampling_steps=num_sampling_steps,
+                                    num_reconstructions=num_reconstructions,
+                                    batch_size=view.batch_size)
+        net.set_condition(condition=condition)
+        try:
+            obs = inverse_problem.observation
+            y_rows = obs.reshape(max(view.batch_size, 1), *operator.y_shape).to(torch.float32)
+            step = FusedDiffPIRStep(net, inverse_problem, y_rows, num_reconstructions,
+                                    guidance_weight=guidance_weight, zeta=zeta,
+                                    min_noise_std=min_noise_std, micro_batch=micro_batch,
+                                    timer=timer)
+            if seed is None and noise_fn is None and rng == "philox":
+                seed = draw_seed()
+            seed = int(seed or 0)
+            x = initial_sample(view.flat_shape, net.device, rng=rng, seed=seed,
+                               sample_offset=sample_offset, noise_fn=noise_fn)
+            ts = host_timesteps(net)
+            for i in range(len(ts) - 1, 1, -1):
+                xi = None
+                if noise_fn is not None:
+                    xi = noise_fn("step", i, tuple(x.shape)).to(device=x.device, dtype=torch.float32)
+                elif rng == "torch":
+                    xi = torch.randn_like(x)
+                step(x, i, ts[i], ts[i - 1], xi=xi, seed=seed, sample_offset=sample_offset)
+            x0_final = view.unflatten(step.predict_x0(x, ts[1]))
+            if num_reconstructions == 1 and not keep_reconstruction_dim:
+                x0_final = x0_final.squeeze(len(batch_shape))
+            return self._as_output(x0_final)
+        finally:
+            net.clear_condition()
+            net.clear_sampling_parameters()

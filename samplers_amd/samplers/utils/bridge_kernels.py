@@ -58,6 +58,40 @@ def x0_coefficients(acp: np.ndarray, t: int) -> tuple[float, float]:
     return float(a), float(k)
 
 
+@dataclass(frozen=True)
+class DiffPIRCoefficients:
+    a: float       # sqrt(acp_t)
+    k: float       # sqrt(1 - acp_t)
+    rho: float     # weight of the proximal data step
+    a_prev: float  # sqrt(acp_prev)
+    c_eps: float   # sqrt(1 - acp_prev) * sqrt(1 - zeta): weight of the effective noise
+    c_xi: float    # sqrt(1 - acp_prev) * sqrt(zeta): weight of the fresh noise
+
+
+def diffpir_coefficients(acp: np.ndarray, t: int, t_prev: int, sigma: float,
+                         guidance_weight: float = 7.0, zeta: float = 0.3,
+                         min_noise_std: float = 1e-3) -> DiffPIRCoefficients:
+    """fp32-rounded scalars of one DiffPIR step (Zhu et al. 2023):
+    ``rho = guidance_weight * max(sigma, min_noise_std)^2 * acp_t / (1 - acp_t)`` and the DDIM-like
+    update ``x' = a_prev z + sqrt(1 - acp_prev) (sqrt(1 - zeta) eps_hat + sqrt(zeta) xi)``.
+    ``a`` and ``k`` are ``x0_coefficients``; the others are computed in fp64 from the fp32-rounded
+    alphas, as ``bridge_coefficients`` does."""
+    if not 0.0 <= float(zeta) <= 1.0:
+        raise ValueError(f"zeta must be in [0, 1], got {zeta}")
+    if not float(guidance_weight) > 0.0:
+        raise ValueError(f"guidance_weight must be positive, got {guidance_weight}")
+    a, k = x0_coefficients(acp, t)
+    a_t = np.float64(np.float32(acp[t]))
+    a_p = np.float64(np.float32(acp[t_prev]))
+    s = max(np.float64(sigma), np.float64(min_noise_std))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = np.float64(guidance_weight) * s * s * a_t / (1 - a_t)
+    k_prev = (1 - a_p) ** 0.5
+    f = lambda v: float(np.float32(v))  # noqa: E731
+    return DiffPIRCoefficients(a, k, f(rho), f(a_p ** 0.5), f(k_prev * (1 - np.float64(zeta)) ** 0.5),
+                               f(k_prev * np.float64(zeta) ** 0.5))
+
+
 def compute_bridge_kernel_statistics(x_ell: Tensor, x_s: Tensor, epsilon_net: EpsilonNetwork,
                                      ell: int, t: int, s: int, eta: float = 1.0) -> BridgeStatistics:
     c = bridge_coefficients(host_alphas_cumprod(epsilon_net), ell, t, s, eta)
