@@ -17,11 +17,19 @@ namespace sp {
 //
 // stats pass (grid: chunks x batch): thread (vector column j, pixel row) accumulates, for its 8
 // channels, either the shifted sums  sum (x~ - s_c), sum (x~ - s_c)^2  (x~ = x + chan_bias,
-// s_c = x~ at the sample's first pixel: no cancellation when |mean| >> std), or for the VJP
+// s_c = x~ at the middle pixel of the chunk, gnb_shift_px: no cancellation when |mean| >> std),
+// or for the VJP
 // sum g, sum g xhat (g = dy' gamma); the pixel rows of a column meet in LDS in a fixed order and
 // one partial per (sample, chunk, channel) is written.  finalize (one wave per (sample, group),
 // fp64, fixed order): forward -> mean, rstd and the per-(n, c) affine of the apply
 // (y = x sc + sh); VJP -> the per-(n, c) coefficients of dx = A dy' + B x + D.
+//
+// The shift is per chunk.  The fp32 partials lose (s_c - mean_c)^2 / var_c times their rounding
+// (~1e-7) where s_c is an outlier of its channel.  One pixel as the shift of every chunk — the
+// sample's first, a corner of the image, as this file had it — put rstd 1e-4 off with 1000 at
+// that corner of a 32 x 32 channel; a pixel per chunk costs at most that chunk's partials (the
+// error shrinks by the number of chunks), corners are no chunk's middle, and the finalize merges
+// the chunks about the group mean in fp64, so shifts that differ between chunks cost nothing.
 // ---------------------------------------------------------------------------------------------
 constexpr int GNB_TARGET_BLOCKS = 2048;
 #ifndef GNB_U
@@ -81,6 +89,10 @@ __device__ __forceinline__ bq_u4 gnb_ld(const u16* __restrict__ x1, const u16* _
     return gnb_load<NT>(x2 + ((nn * hw + p) * c2 + ch - c1));
 }
 
+// The pixel whose x~ is the shift of chunk [p0, p1)'s sums: the stats pass and the finalize form it
+// identically (gnb_shift).
+__device__ __forceinline__ int64_t gnb_shift_px(int64_t p0, int64_t p1) { return p0 + ((p1 - p0) >> 1); }
+
 // MODE 0: forward shifted sums; MODE 1: VJP sums (g, g xhat) given per-(n,c) coefs
 // co = [sc | sh | xs | xo] (each n x c fp32) and gamma (c fp32)
 template <int MODE, bool ACT, bool NT = false>
@@ -109,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void k_gnb_stats(const u16* __restrict__ x1
             }
             if constexpr (MODE == 0) {
                 float f[8];
-                unpack8(gnb_ld(x1, x2, c1, c2, nn, hw, 0, j), f);
+                unpack8(gnb_ld(x1, x2, c1, c2, nn, hw, gnb_shift_px(p0, p1), j), f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) sh[e] = f[e] + cbv[e];
             } else {
@@ -201,45 +213,44 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // row of partials is read by consecutive lanes), each lane sums its pairs in a fixed order in
 // fp64, and the wave meets in a fixed butterfly — a handful of loads per lane instead of a
 // chain of `chunks` dependent loads on cpg lanes (4 of 64 at 128 channels / 32 groups).
+// the shift of channel ch in chunk [p0, p1) of sample nn, as k_gnb_stats MODE 0 forms it
 __device__ __forceinline__ float gnb_shift(const u16* __restrict__ x1, const u16* __restrict__ x2, int c1, int c2,
-                                           const float* __restrict__ cbias, int64_t nn, int64_t hw, int c, int ch) {
+                                           const float* __restrict__ cbias, int64_t nn, int64_t hw, int c, int ch,
+                                           int64_t p0, int64_t p1) {
     const float cbv = cbias ? cbias[nn * c + ch] : 0.f;
-    return (ch < c1 ? bf1(x1[nn * hw * c1 + ch]) : bf1(x2[nn * hw * c2 + ch - c1])) + cbv;
+    const int64_t px = nn * hw + gnb_shift_px(p0, p1);
+    return (ch < c1 ? bf1(x1[px * c1 + ch]) : bf1(x2[px * c2 + ch - c1])) + cbv;
 }
 
 __global__ __launch_bounds__(64) void k_gnb_final_fwd(const u16* __restrict__ x1, const u16* __restrict__ x2, int c1,
                                                       int c2, const float* __restrict__ cbias,
-                                                      const float* __restrict__ part, int chunks, int64_t hw,
-                                                      int groups, float eps, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, float* __restrict__ stats,
-                                                      float* __restrict__ co) {
+                                                      const float* __restrict__ part, int chunks, int chunk_px,
+                                                      int64_t hw, int groups, float eps,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      float* __restrict__ stats, float* __restrict__ co) {
     const int c = c1 + c2, cpg = c / groups, g = blockIdx.x, nn = blockIdx.y, lane = threadIdx.x;
     const int64_t ng = (int64_t)gridDim.y * groups;
     const int pairs = cpg * chunks;
     const float* __restrict__ pb = part + (int64_t)nn * chunks * 2 * c + g * cpg;  // chunk 0, first channel
-    // pass 1: group sum of x~ = sum of the shifted partials + hw * shift per channel
-    double sa = 0.0;
-    for (int i = lane; i < pairs; i += 64) {
-        const int k = i / cpg, cc = i - k * cpg;
-        sa += pb[(int64_t)k * 2 * c + cc];
-    }
-    for (int cc = lane; cc < cpg; cc += 64)
-        sa += (double)hw * gnb_shift(x1, x2, c1, c2, cbias, nn, hw, c, g * cpg + cc);
-    const double cnt = (double)hw * cpg;
-    const double mean = wave_sum_d(sa) / cnt;
-    // pass 2: sum (x~ - mean)^2 = sum_c [S2_c + 2 dm_c S1_c + hw dm_c^2], dm_c = shift_c - mean
-    double sx = 0.0;
+    // One pass over the group's (chunk, channel) pairs, in fp64, about a reference r (the first
+    // pair's shift): with d = shift - r and P the chunk's pixels, sum (x~ - r) = sum of S1 + P d and
+    // sum (x~ - r)^2 = sum of S2 + 2 d S1 + P d^2.  r is one of the group's values, so the
+    // cancellation left in var = E2 - E1^2 is (r - mean)^2 / var times 2^-53.
+    const double r = gnb_shift(x1, x2, c1, c2, cbias, nn, hw, c, g * cpg, 0, std::min<int64_t>(hw, chunk_px));
+    double sa = 0.0, sx = 0.0;
     for (int i = lane; i < pairs; i += 64) {
         const int k = i / cpg, cc = i - k * cpg;
         const float* pp = pb + (int64_t)k * 2 * c + cc;
-        const double dm = (double)gnb_shift(x1, x2, c1, c2, cbias, nn, hw, c, g * cpg + cc) - mean;
-        sx += pp[c] + 2.0 * dm * pp[0];
+        const int64_t p0 = (int64_t)k * chunk_px, p1 = std::min<int64_t>(hw, p0 + chunk_px);
+        const double d = (double)gnb_shift(x1, x2, c1, c2, cbias, nn, hw, c, g * cpg + cc, p0, p1) - r;
+        const double np = (double)(p1 - p0), s1 = pp[0];
+        sa += s1 + np * d;
+        sx += pp[c] + 2.0 * d * s1 + np * d * d;
     }
-    for (int cc = lane; cc < cpg; cc += 64) {
-        const double dm = (double)gnb_shift(x1, x2, c1, c2, cbias, nn, hw, c, g * cpg + cc) - mean;
-        sx += (double)hw * dm * dm;
-    }
-    const double var = std::max(0.0, wave_sum_d(sx) / cnt);
+    const double cnt = (double)hw * cpg;
+    const double m1 = wave_sum_d(sa) / cnt;
+    const double mean = r + m1;
+    const double var = std::max(0.0, wave_sum_d(sx) / cnt - m1 * m1);
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float meanf = (float)mean;
     if (lane == 0) stats[(int64_t)nn * groups + g] = meanf, stats[ng + (int64_t)nn * groups + g] = rstd;
@@ -513,8 +524,9 @@ void gnb_stats_pass(int mode, bool act, bool nt, const u16* x1, const u16* x2, i
 void gnb_final_fwd_pass(const u16* x1, const u16* x2, int c1, int c2, const float* cbias, const float* part, int chunks,
                         int64_t n, int64_t hw, int groups, float eps, const float* gamma, const float* beta,
                         float* stats, float* co, hipStream_t s) {
-    launch(0, k_gnb_final_fwd, final_grid(groups, n), dim3(64), s, x1, x2, c1, c2, cbias, part, chunks, hw, groups, eps,
-           gamma, beta, stats, co);
+    const GnbGeo g = gnb_geo(n, c1 + c2, hw);  // the stats pass's chunking (chunks == g.chunks)
+    launch(0, k_gnb_final_fwd, final_grid(groups, n), dim3(64), s, x1, x2, c1, c2, cbias, part, chunks, g.chunk_px, hw,
+           groups, eps, gamma, beta, stats, co);
 }
 
 void gnb_final_fwd_tiles_pass(const float* part, int tiles, int64_t px, int64_t n, int64_t hw, int c, int groups,

@@ -7,15 +7,29 @@
 // apply + SiLU (+ the bias add), 4-5 HBM passes forward and ~7 backward; here it
 // is 2 kernels each way:
 //   fwd: stats  — shifted sums S1 = sum(x - K), S2 = sum((x - K)^2) per chunk
-//        apply  — mean/rstd from the group's chunk partials, z = silu(x*a_c + b_c)
+//        apply  — mean/rstd from the group's chunk partials, z = silu((x-mean)*a_c + beta_c)
 //   bwd: stats  — A = sum(dy*gamma), B = sum(dy*gamma*xhat) per chunk (y recomputed)
 //        apply  — dx = rstd*(dy*gamma - A/n - xhat*B/n)
 // x is NCHW, so one group (sample n, channels g*Cg .. g*Cg+Cg-1) is one contiguous
 // run of Cg*HW floats; it is cut into chunks (8192-16384 floats, see GN_CHUNK_*), one
 // workgroup each, so the launch fills the chip even at batch 1.  Where the input is
-// float4-aligned, single-pass variants of both directions (below) replace the pairs.  The shift K is the group's first
-// element (removes the cancellation of plain sum/sum-of-squares); chunk partials are
-// combined in a fixed order (deterministic).  All four passes are HBM-bound.
+// float4-aligned, single-pass variants of both directions (below) replace the pairs.
+// The shift K is the fp32 mean of 64 elements (+ their channels' bias): 16 runs of 4 spaced evenly
+// over the group, the first half a stride in (gn_sample_at / gn_shift_of).  var = S2/n - (S1/n)^2 in fp32
+// loses (K - mean)^2 / var times the rounding of the sums (~1e-7), so the shifted form removes
+// the cancellation of plain sum / sum-of-squares only while (K - mean)^2 <~ var.  A single
+// sample as K (the group's first element, as this file had it) breaks that whenever the sample
+// is an outlier: (K - mean)^2 / var is then up to the group size, and rstd was 1e-4 .. 1e-2 off
+// with one corner pixel at 1000 in a group of 2^11 .. 2^17 N(0,1) elements.  With the 64-sample
+// mean, (K - mean)^2 is var / 64 in expectation whatever the bulk distribution, the group's
+// corners are not sampled, and a single sampled outlier of any size moves K by 1/64 of itself:
+// (K - mean)^2 / var <= n / 4096.  (Runs of 4: every wave of a workgroup reads the same 16 cache
+// lines per group.  64 separate elements were 64 lines per wave, as many as the workgroup's own
+// chunk, and cost the forward 7-8 % on groups of 2^14 .. 2^15 elements.)  Every path forms K from the same loads in the same order (one wave's butterfly),
+// so K, and with it every result, is the same bit pattern on all of them.  The normalised value
+// is y = (x - mean) * (rstd gamma) + beta — the difference first, so a mean that is large against
+// the spread costs one rounding of the mean and not also one of mean * rstd * gamma.  Chunk
+// partials are combined in a fixed order (deterministic).  All four passes are HBM-bound.
 
 #define SP_TU 4  // debug-build site numbering (sp_common.h SP_DCHECK)
 #include "sp_common.h"
@@ -172,13 +186,31 @@ __device__ __forceinline__ int chan_of(uint32_t j, const GroupCtx& c, const GnGe
 
 constexpr int GN_UNROLL = 4;
 
+// The shift K (file header): lane l of every wave takes element l % 4 of run l / 4, run r starting
+// at (2r + 1) * (gs / 32) rounded down to a multiple of 4 (small groups: clamped to the last
+// element, so lanes repeat elements), adds its channel's bias, and the wave's butterfly sum / 64
+// is K — the same in every lane, wave, workgroup and kernel.
+__device__ __forceinline__ uint32_t gn_sample_at(uint32_t gs) {
+    const uint32_t l = threadIdx.x & 63u;
+    return min((((2u * (l >> 2) + 1u) * (gs >> 5)) & ~3u) + (l & 3u), gs - 1u);
+}
+
+__device__ __forceinline__ float gn_shift_of(float sample) { return wave_sum(sample) * (1.f / 64.f); }
+
+template <int V>
+__device__ __forceinline__ float gn_shift(const GroupCtx& c, const GnGeom& G) {
+    const uint32_t e = gn_sample_at(G.gs);
+    SP_DCHECK(e < G.gs);
+    return gn_shift_of(*c.x.at(e) + (G.bias ? G.bias[c.n * G.C + chan_of<V>(e / V, c, G)] : 0.f));
+}
+
 // ---- forward: chunk partial shifted moments ----------------------------------------
 template <int V>
 __global__ __launch_bounds__(kBlock) void k_gn_stats(const float* __restrict__ x, GnGeom G,
                                                      float* __restrict__ partial) {
     __shared__ float red[8];
     const GroupCtx c = group_ctx<V>(x, G);
-    const float K = *c.x.at(0) + (G.bias ? G.bias[c.n * G.C + c.g * G.Cg] : 0.f);
+    const float K = gn_shift<V>(c, G);
     float s1 = 0.f, s2 = 0.f;
     for (uint32_t j0 = c.lo + threadIdx.x; j0 < c.hi; j0 += GN_UNROLL * kBlock) {
         float v[GN_UNROLL][V];
@@ -233,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void k_gn_apply(const float* __restrict__ x
     const GroupCtx c = group_ctx<V>(x, G);
     float S1, S2;
     group_sums(partial, G.chunks, S1, S2);
-    const float K = *c.x.at(0) + (G.bias ? G.bias[c.n * G.C + c.g * G.Cg] : 0.f);
+    const float K = gn_shift<V>(c, G);
     const float inv_n = 1.f / static_cast<float>(G.gs);
     const float m1 = S1 * inv_n;
     const float mean = K + m1;
@@ -255,11 +287,11 @@ __global__ __launch_bounds__(kBlock) void k_gn_apply(const float* __restrict__ x
             const int ch = chan_of<V>(j, c, G);
             const float b = G.bias ? G.bias[c.n * G.C + ch] : 0.f;
             const float sc = rstd * (G.gamma ? G.gamma[ch] : 1.f);
-            const float sh = (G.beta ? G.beta[ch] : 0.f) - mean * sc;
+            const float be = G.beta ? G.beta[ch] : 0.f;
             float o[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                const float y = fmaf(v[u][e] + b, sc, sh);
+                const float y = fmaf(v[u][e] + b - mean, sc, be);
                 o[e] = ACT ? silu_f(y) : y;
             }
             store_v<V>(zg + (size_t)j * V, o);
@@ -267,7 +299,11 @@ __global__ __launch_bounds__(kBlock) void k_gn_apply(const float* __restrict__ x
     }
 }
 
-// dy*gamma and xhat for one element group (y recomputed exactly as the forward did).
+// dy*gamma and xhat for one element group.  y, which only SiLU's derivative reads, is recomputed
+// as x * sc + sh: up to 2^-23 |mean| rstd gamma from the forward's centred form, which moves
+// silu'(y) by less than the fp32 mean itself moves xhat (the centred form here measured 1.6 %
+// slower on the single-pass VJP at 64 x 128 x 256^2 with fewer instructions: the schedule around
+// the poll and the prefetch is what that kernel's time hangs on).
 template <int V, bool ACT>
 __device__ __forceinline__ void gn_grad_terms(const float (&v)[V], const float (&dz)[V], float b,
                                               float mean, float rstd, float ga, float be,
@@ -522,9 +558,9 @@ constexpr int GNP_MAX_CG = 128;  // channels per group the LDS table holds
 
 struct GnpBuf {  // one group's per-thread prefetch state besides the chunk itself
     float ga, be, bi;  // thread t < Cg: gamma / beta / bias of the group's channel t
-    float kx, kb;      // the group's first element and that channel's bias: the shift K is
-                       // their sum, formed where it is used (forming it here would wait for
-                       // the whole prefetch)
+    float kx, kb;      // this lane's sample of the group (gn_sample_at) and its channel's bias:
+                       // the shift K is the wave's mean of their sums (gn_shift_of), formed
+                       // where it is used (forming it here would wait for the whole prefetch)
 };
 
 // Issue the loads of group gi's chunk m and its per-channel state.  live == false: the chunk
@@ -548,8 +584,9 @@ __device__ __forceinline__ void gnp_issue(const float* __restrict__ base, const 
     b.ga = G.gamma ? ga : 1.f;
     b.be = G.beta ? be : 0.f;
     b.bi = G.bias ? bi : 0.f;
-    b.kx = *c.x.at(0);
-    const float kb = (G.bias ? G.bias : base)[c.n * G.C + c.g * G.Cg];
+    const uint32_t ks = gn_sample_at(G.gs);
+    b.kx = *c.x.at(ks);
+    const float kb = (G.bias ? G.bias : base)[c.n * G.C + chan_of<4>(ks / 4, c, G)];
     b.kb = G.bias ? kb : 0.f;
 }
 
@@ -666,7 +703,7 @@ __device__ __forceinline__ void gnp_fwd_group(const float* __restrict__ x, const
     SP_DCHECK(G.Cg <= GNP_MAX_CG);  // the group's channels fit the LDS table
     if (t < G.Cg) tab[0][t] = bf.ga, tab[1][t] = bf.be, tab[2][t] = bf.bi;
     __syncthreads();
-    const float K = bf.kx + bf.kb;
+    const float K = gn_shift_of(bf.kx + bf.kb);  // as gn_shift<4>
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
@@ -704,11 +741,11 @@ __device__ __forceinline__ void gnp_fwd_group(const float* __restrict__ x, const
         const uint32_t cl = fdiv(j < c.hi ? j : c.lo, G.hw_div);
         const float b = G.bias ? tab[2][cl] : 0.f;
         const float sc = rstd * tab[0][cl];
-        const float sh = tab[1][cl] - mean * sc;
+        const float be = tab[1][cl];
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float y = fmaf(v[i][e] + b, sc, sh);
+            const float y = fmaf(v[i][e] + b - mean, sc, be);
             o[e] = ACT ? silu_f(y) : y;
         }
         gnt_store(rz, vo, i, o);  // past the chunk end: dropped

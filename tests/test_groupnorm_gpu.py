@@ -155,19 +155,28 @@ def test_fused_resnet_blocks_match_cpu(cuda):
     assert _rel(gx.cpu(), gref) < 1e-4
 
 
-@pytest.mark.parametrize("shape", [  # (n, c1, c2, h, w, groups)
+_BITWISE_SHAPES = [  # (n, c1, c2, h, w, groups)
     (2, 128, 128, 64, 64, 32),    # 8 channels per group, 4 chunks per group
     (3, 64, 0, 48, 48, 32),       # 2 channels x 2304: one partial chunk
     (2, 128, 0, 256, 256, 32),    # 16 chunks per group
     (5, 256, 256, 8, 8, 32),      # many small groups: several groups per team
     (2, 96, 32, 16, 16, 32),      # c1 % (channels per group) == 0 with a 2-part split
     (1, 256, 128, 128, 128, 32),  # a group straddles the parts at a chunk boundary (UNet 128^2)
-])
+]
+# value 0: the inputs as drawn; 2 / 4 / 7: tests/gn_ref.py's value cases (the group's first element
+# 1000, its first image row 100, mean 1e3 over a spread of 1e-2) applied to them, on two shapes —
+# the shift K of the moments must be formed identically on every path whatever it is formed from
+_BITWISE = [pytest.param(s, 0, id=f"shape{i}") for i, s in enumerate(_BITWISE_SHAPES)] + [
+    pytest.param(_BITWISE_SHAPES[i], v, id=f"shape{i}-case{v}") for i in (0, 5) for v in (2, 4, 7)]
+
+
+@pytest.mark.parametrize("shape,value", _BITWISE)
 @pytest.mark.parametrize("act", [True, False])
-def test_single_pass_matches_two_pass_bitwise(cuda, shape, act, monkeypatch):
+def test_single_pass_matches_two_pass_bitwise(cuda, shape, value, act, monkeypatch):
     """The single-pass team kernels (one workgroup per chunk, chunk partials exchanged through
     agent-scope atomics) against the two-pass kernels: same chunking, same summation order,
     so the forward output, statistics and the input VJP agree bit for bit."""
+    import gn_ref
     from samplers_amd import _hip
     from samplers_amd.networks.layers import _team_regions, gn_backward, gn_forward
 
@@ -180,9 +189,14 @@ def test_single_pass_matches_two_pass_bitwise(cuda, shape, act, monkeypatch):
         layer.weight.copy_(1 + 0.3 * torch.randn(c, generator=gen))
         layer.bias.copy_(0.2 * torch.randn(c, generator=gen))
     layer = layer.to(cuda)
-    x1 = (torch.randn(n, c1, h, w, generator=gen) * 2 + 0.5).to(cuda)
-    x2 = (torch.randn(n, c2, h, w, generator=gen) - 0.3).to(cuda) if c2 else None
-    cb = torch.randn(n, c, generator=gen).to(cuda)
+    x1 = torch.randn(n, c1, h, w, generator=gen) * 2 + 0.5
+    x2 = torch.randn(n, c2, h, w, generator=gen) - 0.3 if c2 else None
+    cb = torch.randn(n, c, generator=gen)
+    if value:
+        xc = torch.cat([x1, x2], 1) if c2 else x1
+        gn_ref.apply_case(value, xc, cb, g)
+        x1, x2 = (xc[:, :c1].contiguous(), xc[:, c1:].contiguous()) if c2 else (xc, None)
+    x1, x2, cb = x1.to(cuda), (x2.to(cuda) if c2 else None), cb.to(cuda)
     dz = torch.randn(n, c, h, w, generator=gen).to(cuda)
     a1 = torch.randn(n, c1, h, w, generator=gen).to(cuda)
     a2 = torch.randn(n, c2, h, w, generator=gen).to(cuda) if c2 else None
