@@ -91,7 +91,7 @@ enum {
                            Linear, m == n; sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
                            sp_op_pinv_ws = A^+ / A^+T, sp_pgdm_prepare and
                            sp_pgdm_residual_ws the fused PGDM pass 1             */
-    SP_OP_RADON = 9     /* new: parallel-beam CT projector (Joseph's method, unit pixel
+    SP_OP_RADON = 9,    /* new: parallel-beam CT projector (Joseph's method, unit pixel
                            and detector spacing), depthwise over channel planes:
                            y is (channels, radius, factor) = (C, angles, detector
                            bins), m = channels*radius*factor != n in general;
@@ -99,6 +99,20 @@ enum {
                            1 <= factor <= 1024 bins; taps holds one row per angle
                            (below).  Linear, adjoint = exact transpose (a gather per
                            pixel, no atomics); no pseudo-inverse                */
+    SP_OP_SR_PERIODIC = 10 /* new: periodic blur-and-decimate x factor super-resolution
+                           (bicubic, Gaussian blur + decimation), depthwise:
+                           y[c][i][j] = sum_{u,v} h[u][v] x[c][(factor*i + u - P) mod H]
+                           [(factor*j + v - P) mod W] over radius^2 taps, P = (radius -
+                           factor) / 2.  factor 2, 4 or 8 dividing height and width,
+                           each 2^k or 3*2^k in [8, 1024]; factor <= radius <=
+                           min(height, width), radius - factor even; m = n / factor^2.
+                           A = S IFFT2 M FFT2 with S the lattice [::factor, ::factor],
+                           so A A^T is diagonal in the low-resolution transform: exact
+                           transpose, spectral pseudo-inverse and closed-form proximal
+                           map; taps holds M, P and Lambda (below).  The maps need a
+                           workspace: sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
+                           sp_op_pinv_ws = A^+ / A^+T, and the fused PGDM and prox
+                           passes as PSF_PERIODIC                                 */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -130,7 +144,18 @@ typedef struct sp_op {
                                         P = 1/M on the kept frequencies and 0 on the
                                         others, the multiplier of A^+.  P must be
                                         conjugate-symmetric under k -> -k like M (a
-                                        symmetric kept set).  RADON: 4*radius floats,
+                                        symmetric kept set).  SR_PERIODIC: M (tap
+                                        (u, v) at ((u-P) mod H, (v-P) mod W)) and P in
+                                        that layout, then Lambda_t as plain fp32
+                                        [width/2+1][height], 5*(width/2+1)*height floats
+                                        in all.  With s = factor, on the (H/s, W/s)
+                                        grid Lambda[kh][kw] = (1/s^2) sum_{a,b<s}
+                                        |M[kh + a H/s][kw + b W/s]|^2; Lambda_t is
+                                        Lambda tiled s x s to H x W, and P =
+                                        conj(M) / Lambda_t where sqrt(Lambda) exceeds
+                                        the caller's threshold, 0 elsewhere (tiled
+                                        alike).  All computed in fp64 by the caller
+                                        and rounded to fp32.  RADON: 4*radius floats,
                                         one row (alpha, beta, length, axis) per angle
                                         theta: axis 0 (|cos| >= |sin|): (1/cos,
                                         -sin/cos, 1/|cos|, 0), ray s crosses image row
@@ -149,15 +174,17 @@ typedef struct sp_op {
     int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
                                         zero rows added above and below.  PSF_FFT:
                                         1..min(height, width) - 1.  PSF_PERIODIC:
-                                        1..(min(height, width) - 1) / 2.  RADON: the
+                                        1..(min(height, width) - 1) / 2.  SR_PERIODIC:
+                                        the taps per axis K, factor..min(height,
+                                        width), K - factor even.  RADON: the
                                         number of angles, 1..512                 */
-    int32_t factor;                  /* SR: 2, 4 or 8.  PHASE: pad_w >= 0, zero
+    int32_t factor;                  /* SR, SR_PERIODIC: 2, 4 or 8.  PHASE: pad_w >= 0, zero
                                         columns added left and right.  PSF_FFT: the
                                         boundary: 0 reflect, 1 circular, 2 zeros (0
                                         for the other kinds).  RADON: the number of
                                         detector bins, 1..1024.  PHASE: keep_bits,
                                         word_rank and taps must be NULL; PSF_FFT
-                                        and PSF_PERIODIC: keep_bits and word_rank;
+                                        PSF_PERIODIC and SR_PERIODIC: keep_bits and word_rank;
                                         RADON: keep_bits and word_rank too       */
 } sp_op;
 
@@ -243,8 +270,12 @@ int sp_debug_selftest(sp_stream_t stream);
  * m == n == channels*height*width and keep_bits and word_rank are NULL.  PSF_PERIODIC: the same
  * count with Nw = width; rejected unless taps != NULL, factor == 0, height and width are each 2^k
  * or 3*2^k in [8, 1024], radius >= 1, 2*radius + 1 <= min(height, width),
- * m == n == channels*height*width and keep_bits and word_rank are NULL.  RADON: the workgroups
- * per sample of its project launch, channels * radius * ceil(factor / 256) (csrc/sp_radon.hip);
+ * m == n == channels*height*width and keep_bits and word_rank are NULL.  SR_PERIODIC: the tiles
+ * of min(lines of a width-point transform, height / factor) lattice rows per sample of its fused
+ * launch; rejected unless taps != NULL, factor is 2, 4 or 8 and divides height and width, each 2^k
+ * or 3*2^k in [8, 1024], factor <= radius <= min(height, width), radius - factor even,
+ * n == channels*height*width, m * factor^2 == n and keep_bits and word_rank are NULL.  RADON: the
+ * workgroups per sample of its project launch, channels * radius * ceil(factor / 256) (csrc/sp_radon.hip);
  * rejected unless taps != NULL, 1 <= radius <= 512, 1 <= factor <= 1024, 8 <= height, width <= 512,
  * n == channels*height*width, m == channels*radius*factor and keep_bits and word_rank are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
@@ -252,12 +283,13 @@ int64_t sp_rsq_partials(const sp_op* op);
  * 0 for every kind but those below (one pass, no workspace), batch * m for PSF (its residual launch
  * leaves grad_scale * r there for the adjoint launch), 2 * batch * channels * Nw * height for
  * PHASE (the complex row transforms, stored transposed), 2 * batch * channels * (Nw/2 + 1) * height
- * for PSF_FFT (the same, half the spectrum: the rows are real) and for PSF_PERIODIC (Nw = width),
+ * for PSF_FFT (the same, half the spectrum: the rows are real) and for PSF_PERIODIC and SR_PERIODIC
+ * (Nw = width),
  * batch * m for RADON (grad_scale * r in sinogram space, between project and backproject).  SP_EINVAL for a rejected
  * descriptor or batch <= 0.  The library allocates nothing. */
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
 /* Floats of `work` that sp_op_apply_ws / sp_op_vjp_ws need: 0 for the linear kinds, the figure
- * of sp_dps_workspace for PHASE, PSF_FFT and PSF_PERIODIC (sp_op_pinv_ws and
+ * of sp_dps_workspace for PHASE, PSF_FFT, PSF_PERIODIC and SR_PERIODIC (sp_op_pinv_ws and
  * sp_pgdm_residual_ws take the same).  SP_EINVAL for a rejected descriptor or batch <= 0. */
 int64_t sp_op_workspace(const sp_op* op, int64_t batch);
 
@@ -297,7 +329,11 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  * per row tile the inverse row FFT, g = grad_scale * (y - A x0), one r^2 partial and the forward
  * row FFT of g; the column launch again with the spectrum and the fold; inverse row FFTs and the
  * fold -> v = A^T g.  PSF_PERIODIC: the same five launches on exact-size transforms (Nh = height,
- * Nw = width), nothing extended or folded.  RADON runs here only too, as two launches
+ * Nw = width), nothing extended or folded.  SR_PERIODIC: five launches too: row FFTs of x0; the
+ * column launch with M, which stores the height / factor lattice rows alone; per tile of lattice
+ * rows the inverse row FFT, g = grad_scale * (y - A x0) on the lattice columns, one r^2 partial,
+ * g zero-inserted along the row and transformed forward; the column launch that inserts the zero
+ * rows in LDS, with conj(M); inverse row FFTs -> v = A^T g.  RADON runs here only too, as two launches
  * (csrc/sp_radon.hip): `project` forms x0 while it stages its slab of the plane, sums every ray in
  * row (column) order, writes work = grad_scale * (y - A x0) and one |r|^2 partial per workgroup;
  * `backproject` gathers v = A^T work per pixel, angles in order.  The result has the same bits on
@@ -352,18 +388,22 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
  * unused, may be NULL); PHASE: y = |FFT2(pad(x))| (sp_op_apply and sp_op_adjoint return
  * SP_EUNSUPPORTED for PHASE, as do sp_psld_pixel, sp_psld_cotangent and sp_pixel_opt_step);
  * PSF_FFT: y = A x, the extended correlation (the same entries return SP_EUNSUPPORTED for it);
- * PSF_PERIODIC: y = A x = Re IFFT2(FFT2(x) * M), likewise. */
+ * PSF_PERIODIC: y = A x = Re IFFT2(FFT2(x) * M), likewise; SR_PERIODIC: the lattice
+ * [::factor, ::factor] of that, y of m = n / factor^2 (the column launch stores the lattice rows
+ * alone, the inverse-row launch transforms those and stores the lattice columns). */
 int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
                    sp_stream_t stream);
 /* dx = J(x)^T g for the nonlinear kinds (g: batch rows of m, dx: batch rows of n).  PHASE:
  * crop(Re(IFFT2(g * z/|z|))) with z = FFT2(pad(x)) recomputed, z/|z| = 0 at |z| = 0 (never NaN
  * or inf).  PSF_FFT: dx = A^T g, the exact adjoint (x is not read); PSF_PERIODIC the same, with
- * the multiplier conj(M).  SP_EUNSUPPORTED for the
+ * the multiplier conj(M); SR_PERIODIC: dx = Re IFFT2(FFT2(up g) * conj(M)), up the zero insertion
+ * onto the lattice (only the lattice rows are read and row-transformed; the column launch inserts
+ * the zero rows in LDS).  SP_EUNSUPPORTED for the
  * linear kinds without a workspace, whose VJP is sp_op_adjoint. */
 int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
                  float* work, sp_stream_t stream);
 
-/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC); SP_EUNSUPPORTED for every other kind, SP_EINVAL
+/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC, SR_PERIODIC); SP_EUNSUPPORTED for every other kind, SP_EINVAL
  * for a rejected descriptor or argument first.  No reference counterpart: the reference's
  * SVDOperator.apply_pseudo_inverse (linear.py) is the dense form of the same map.
  *   sp_op_pinv_ws        x = A^+ y = Re IFFT2(FFT2(y) * P) (transpose = 0) or A^+T y (transpose =
@@ -381,6 +421,12 @@ int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int
  *                        z <- grad_scale * (q[b / y_div] - (P != 0 ? z / (H W) : 0)) and the inverse
  *                        column FFT, in LDS; inverse row FFTs, real part -> v.  Sample b uses
  *                        row b / y_div of q.  Pass 2 is sp_dps_update with rsq_partial = NULL.
+ * SR_PERIODIC: sp_op_pinv_ws is x = Re IFFT2(FFT2(up y) * P) (y: rows of m, x: rows of n) or, with
+ * transpose = 1, the lattice of Re IFFT2(FFT2(y) * conj(P)) (y: rows of n, x: rows of m).
+ * sp_pgdm_prepare copies each observation row (m floats) to the head of its row of q (q sized and
+ * strided as above: the residual is formed on the lattice, where y is 2 factor^2 times smaller
+ * than a spectrum of up y); sp_pgdm_residual_ws is v = grad_scale * A^+ (y - A x0) in the five
+ * launches of its DPS pass 1 with P in the second column launch and no partials.
  * work and q must not alias any other argument. */
 int sp_op_pinv_ws(const sp_op* op, const float* y, float* x, int64_t batch, int32_t transpose,
                   float* work, sp_stream_t stream);
@@ -398,6 +444,8 @@ int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const
  *   SR x s (A A^T = I / s^2)              z = x0 + (r replicated over its block) / (1 + rho s^2),
  *                                         the block mean of x0 in the order of csrc/sp_sr.hip;
  *   PSF_PERIODIC (A = IFFT2 M FFT2)       Z = (conj(M) Y + rho X0) / (|M|^2 + rho), z = Re IFFT2(Z).
+ *   SR_PERIODIC (A A^T diagonal, Lambda)  z = x0 + Re IFFT2(FFT2(up r) conj(M) / (Lambda_t + rho)):
+ *                                         every frequency divided, not only the kept ones;
  * Every other kind: SP_EUNSUPPORTED (after the common argument checks, which answer SP_EINVAL).
  * The scalars are applied as reciprocals computed once per thread (1 / a, 1 / k, 1 / (1 + rho s^2),
  * 1 / (|M|^2 + rho)), as sp_dps_update does.  Plain stores, no atomics; every sample is computed
@@ -411,22 +459,25 @@ typedef struct sp_prox_coefs {
     float c_xi;   /* sqrt(1 - alpha_bar[t_prev]) * sqrt(zeta)                 */
 } sp_prox_coefs;  /* 24 bytes */
 /* Floats of `work` that sp_op_prox_ws / sp_diffpir_step_ws need for `batch` samples: 0 for the
- * elementwise kinds and SR, the sp_op_workspace figure for PSF_PERIODIC.  This is the capability
+ * elementwise kinds and SR, the sp_op_workspace figure for PSF_PERIODIC and SR_PERIODIC.  This is the capability
  * probe: SP_EUNSUPPORTED for a valid kind without a closed-form prox, SP_EINVAL for a rejected
  * descriptor or batch <= 0. */
 int64_t sp_prox_workspace(const sp_op* op, int64_t batch);
-/* Floats of `q` for `rows` observation rows: 0 but for PSF_PERIODIC,
+/* Floats of `q` for `rows` observation rows: 0 but for PSF_PERIODIC and SR_PERIODIC,
  * 2 * rows * channels * (width/2 + 1) * height there.  Codes as sp_prox_workspace. */
 int64_t sp_prox_prepare_size(const sp_op* op, int64_t rows);
 /* q = conj(M) * FFT2(y) / (H W) per observation row, as (re, im) pairs
  * [row][channels][width/2 + 1][height] (the intermediate's layout): sp_pgdm_prepare's two launches
- * with the multiplier conj(M).  Once per sampler call.  The kinds whose sp_prox_prepare_size is 0:
+ * with the multiplier conj(M); SR_PERIODIC: the copy of sp_pgdm_prepare.  Once per sampler call.
+ * The kinds whose sp_prox_prepare_size is 0:
  * SP_OK, nothing launched, q may be NULL. */
 int sp_prox_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_stream_t stream);
 /* z_out = prox(x0; y, rho) for `batch` rows of x0, sample b against observation row b / y_div.
  * One launch (elementwise kinds, SR: y read, q and work may be NULL) or three (PSF_PERIODIC: row
  * FFTs of x0 -> work; per column tile z <- (q[b / y_div] + rho z / (H W)) / (|M|^2 + rho) between
- * the transforms; inverse row FFTs, real part -> z_out; q and work required, y not read).
+ * the transforms; inverse row FFTs, real part -> z_out; q and work required, y not read) or five
+ * (SR_PERIODIC: its DPS pass 1 with grad_scale = 1, no partials and conj(M) / (Lambda_t + rho) in
+ * the second column launch; the last launch adds x0 in space; q and work required, y not read).
  * z_out may alias x0; work and q must not alias any other argument. */
 int sp_op_prox_ws(const sp_op* op, const float* x0, const float* y, const float* q, int64_t batch,
                   int64_t y_div, float rho, float* z_out, float* work, sp_stream_t stream);

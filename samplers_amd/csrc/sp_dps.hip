@@ -590,12 +590,20 @@ static const op_kind g_kinds[] = {
     {radon_valid, radon_partials, radon_workspace, nullptr, radon_dps_residual, radon_apply,
      radon_adjoint, nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
      SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
+    /* SP_OP_SR_PERIODIC: the periodic kind's columns with a lattice between the transforms: every
+       pass PSF_PERIODIC has, y of (C, H / s, W / s) */
+    {sr_periodic_valid, sr_periodic_partials, psf_fft_workspace, psf_fft_workspace,
+     sr_periodic_dps_residual, nullptr, nullptr, sr_periodic_apply, sr_periodic_vjp, nullptr,
+     nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
+     sr_periodic_pinv, sr_periodic_pgdm_prepare, sr_periodic_pgdm_residual, psf_fft_workspace,
+     sr_periodic_prox_prepare, sr_periodic_prox, sr_periodic_prox},
 };
 #undef SP_ELEMENTWISE_ROW
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
-                  SP_OP_PSF_PERIODIC == 8 && SP_OP_RADON == 9 && kKinds == 10,
+                  SP_OP_PSF_PERIODIC == 8 && SP_OP_RADON == 9 && SP_OP_SR_PERIODIC == 10 &&
+                  kKinds == 11,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -613,7 +621,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 109; }
+int sp_version(void) { return 110; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 

@@ -108,5 +108,15 @@ psld_cotangent_fn elementwise_psld_cotangent, sr_psld_cotangent;
 pixel_opt_fn elementwise_pixel_opt, sr_pixel_opt;
 pgdm_prepare_fn psf_periodic_prox_prepare;
 prox_fn sr_prox, psf_periodic_prox;  // both forms: p.eps selects (elementwise kinds: sp_dps.hip)
+// SP_OP_SR_PERIODIC (sp_psf_fft.hip, on the periodic kind's pipeline; psf_fft_workspace serves it)
+valid_fn sr_periodic_valid;
+partials_fn sr_periodic_partials;
+dps_residual_fn sr_periodic_dps_residual;
+apply_ws_fn sr_periodic_apply;
+vjp_ws_fn sr_periodic_vjp;
+pinv_ws_fn sr_periodic_pinv;
+pgdm_prepare_fn sr_periodic_pgdm_prepare, sr_periodic_prox_prepare;
+pgdm_residual_fn sr_periodic_pgdm_residual;
+prox_fn sr_periodic_prox;
 
 }  // namespace sp

@@ -40,6 +40,8 @@
 // SP_OP_PSF_PERIODIC runs the same kernels on exact-size transforms, Nh = H and Nw = W, where the
 // wrap-around blur is diagonal: nothing extended or folded, and a pseudo-inverse that is one more
 // multiplier.  The host section at the end of the file launches both kinds through one pipeline.
+// SP_OP_SR_PERIODIC (the k_srp_* kernels below and the last host section) puts the lattice
+// [::s, ::s] between the periodic kind's transforms: blur-and-decimate super-resolution.
 
 #include <algorithm>
 
@@ -50,13 +52,15 @@
 namespace sp {
 
 enum { PF_REFLECT = 0, PF_CIRCULAR = 1, PF_ZEROS = 2 };
-enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2, PF_OUT_PROX = 3 };
+enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2, PF_OUT_PROX = 3, PF_OUT_PROX_ADD = 4 };
 enum { PF_COL_MAP = 0, PF_COL_PREPARE = 1, PF_COL_PGDM = 2, PF_COL_PROX = 3 };
 
 // what the PF_OUT_PROX epilogue of k_pf_rows_inv needs besides z (the other forms pass an empty
-// one): step != 0 forms eps_hat from x and writes the DiffPIR sample, else z itself
+// one): step != 0 forms eps_hat from x and writes the DiffPIR sample, else z itself.
+// PF_OUT_PROX_ADD (SP_OP_SR_PERIODIC): the transform holds z - x0, and x0 (x itself, or
+// (x - k eps) / a in the step form) is added in space first
 struct pf_prox_tail {
-    const float *x, *xi;
+    const float *x, *xi, *eps;
     uint64_t seed;
     int64_t step, sample_offset;
     sp_prox_coefs c;
@@ -73,6 +77,8 @@ static int pf_size(int n) {
 struct pf_geom {  // filled on the host from a valid descriptor (pf_geometry)
     int C, H, W, R, mode, Nh, Nw, HW;  // HW = Nw / 2 + 1 stored columns
     const float2* spec;                // [HW][Nh]
+    int s;                             // SP_OP_SR_PERIODIC: the lattice stride (1 for the others)
+    const float* lam;                  // SP_OP_SR_PERIODIC: Lambda_t [HW][Nh]
 };
 
 // source pixel of extended position p in [0, n + 2R) along an axis of n pixels; -1: a zero
@@ -337,11 +343,12 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
                 wp[kw * g.H + h] = f[t * NP + phase_slot(kw)];
             }
         }
-    } else if constexpr (OUT == PF_OUT_PROX) {
+    } else if constexpr (OUT == PF_OUT_PROX || OUT == PF_OUT_PROX_ADD) {
         // z = the real part; four columns per thread (W % 4 == 0 for every transform length), so
         // x, xi and the output move as float4 and one Philox draw serves its four elements
         float* __restrict__ op_out = out + plane * g.H * g.W;
-        const float* __restrict__ xp = px.step_form ? px.x + plane * g.H * g.W : nullptr;
+        const float* __restrict__ xp =
+            px.step_form || OUT == PF_OUT_PROX_ADD ? px.x + plane * g.H * g.W : nullptr;
         const float* __restrict__ nzp = px.xi ? px.xi + plane * g.H * g.W : nullptr;
         const float inv_k = px.step_form ? 1.f / px.c.k : 1.f;
         const int groups = g.W / 4;
@@ -354,6 +361,18 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
             float o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = rl[phase_slot(j + e)].x;
+            if constexpr (OUT == PF_OUT_PROX_ADD) {
+                float x0[4];
+                load_v<4>(xp + h * g.W + j, x0);
+                if (px.step_form) {  // the x0 of launch 1
+                    float ev[4];
+                    load_v<4>(px.eps + plane * g.H * g.W + h * g.W + j, ev);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x0[e] = (x0[e] - px.c.k * ev[e]) / px.c.a;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] += x0[e];
+            }
             if (px.step_form) {
                 const int64_t el = (int64_t)c * g.H * g.W + h * g.W + j;  // flat element index
                 float xv[4], nz[4];
@@ -393,6 +412,224 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// SP_OP_SR_PERIODIC: periodic blur-and-decimate super-resolution (operators/sr_periodic.py, pinned
+// in fp64 by tests/sr_periodic_ops.py).  With s = op.factor, S the lattice [::s, ::s] and up = S^T
+// (zero insertion), on exact-size transforms (Nh = H, Nw = W) as the periodic kind:
+//   A x     = S IFFT2(FFT2(x) M)          A^T y = IFFT2(FFT2(up y) conj(M))
+//   A^+T x  = S IFFT2(FFT2(x) conj(P))    A^+ y = IFFT2(FFT2(up y) P)
+// Down (A, A^+T): k_pf_rows on the H rows, k_srp_cols<false> (stores the H / s lattice rows alone,
+// compacted to the head of each column), k_srp_rows_inv<false> (transforms those rows, stores the
+// W / s lattice columns).  Up (A^T, A^+): k_srp_rows_up (reads the (H / s) x (W / s) input,
+// transforms the lattice rows alone), k_srp_cols<true> (inserts the zero rows in LDS),
+// k_pf_rows_inv<PF_OUT_A>.  No launch reads, transforms or writes a row that is identically zero.
+// The fused passes are down, then k_srp_rows_inv<true> on the lattice rows (g = gs (y - A x0), its
+// r^2 partial, g zero-inserted along the row and transformed forward again), then up with
+// conj(M) (DPS), P (PGDM) or conj(M) / (Lambda_t + rho) (prox), then the full inverse rows.
+// Every sample alone, lines assigned by plane and tile, block_sum's fixed order, plain stores.
+// ---------------------------------------------------------------------------
+// launch 2.  UP false: H values a column in, the lattice rows h = s i out at [i], i < H / s.
+// UP true: H / s values in from [i], placed at s i of a zero column, H values out.  Between the
+// transforms times spec (conj_sign -1: its conjugate) / (H W); PROX: and / (Lambda_t + rho).
+template <bool UP, bool PROX>
+__global__ __launch_bounds__(kBlock) void k_srp_cols(pf_geom g, float2* __restrict__ ws, int T,
+                                                     float conj_sign, float rho) {
+    static_assert(UP || !PROX, "the prox multiplier belongs to the up launch");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int N = g.H, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.HW + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int kw0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    const int sh = __ffs(g.s) - 1, Hl = g.H >> sh;
+    SP_DCHECK(c < g.C && kw0 < g.HW && N == g.Nh && g.s == (1 << sh) && (Hl << sh) == g.H);
+    float2* __restrict__ wp = ws + (plane * g.HW + kw0) * (int64_t)g.H;  // the tile's columns
+    const int lines = min(T, g.HW - kw0);
+
+    phase_twiddles(tw, N);
+    for (int t = 0; t < T; ++t)
+        for (int q = threadIdx.x; q < N; q += kBlock) {
+            float2 val = make_float2(0.f, 0.f);
+            if (t < lines && (!UP || (q & (g.s - 1)) == 0)) {
+                const int h = UP ? q >> sh : q;
+                SP_DCHECK(h < (UP ? Hl : g.H));
+                val = wp[t * g.H + h];
+            }
+            A[t * NP + phase_slot(q)] = val;
+        }
+    __syncthreads();
+    float2* z = phase_fft(A, B, tw, N, NP, T, false);
+
+    const float sc = 1.f / ((float)g.H * (float)g.W);
+    const float2* __restrict__ hsp = g.spec + (int64_t)kw0 * N;
+    const float* __restrict__ lam = PROX ? g.lam + (int64_t)kw0 * N : nullptr;
+    const int total = lines * N;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int t = idx / N, kh = idx - t * N;
+        SP_DCHECK(t < lines && kw0 + t < g.HW && kh < g.H);
+        float2 m = hsp[idx];
+        float f = sc;
+        if constexpr (PROX) f = sc / (lam[idx] + rho);
+        m.x *= f;
+        m.y *= conj_sign * f;
+        float2* zp = z + t * NP + phase_slot(kh);
+        *zp = cmul(*zp, m);
+    }
+    __syncthreads();
+    const float2* u = phase_fft(z, z == A ? B : A, tw, N, NP, T, true);
+    const int rows = UP ? g.H : Hl, keep = lines * rows;
+    for (int idx = threadIdx.x; idx < keep; idx += kBlock) {
+        const int t = idx / rows, i = idx - t * rows, h = UP ? i : i << sh;
+        SP_DCHECK(t < lines && h < g.H && t * g.H + i < lines * g.H);
+        wp[t * g.H + i] = u[t * NP + phase_slot(h)];
+    }
+}
+
+// launch 1 of the up maps: T rows of the (H / s) x (W / s) input, each zero-inserted onto the
+// lattice columns, W-point FFT, the half spectrum stored transposed at [kw][i], i < H / s
+__global__ __launch_bounds__(kBlock) void k_srp_rows_up(pf_geom g, const float* __restrict__ in,
+                                                        float2* __restrict__ ws, int T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int N = g.W, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int sh = __ffs(g.s) - 1, Hl = g.H >> sh, Wl = g.W >> sh;
+    const int tiles = (Hl + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int i0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    SP_DCHECK(c < g.C && i0 < Hl && N == g.Nw && g.s == (1 << sh) && (Wl << sh) == g.W);
+    const float* __restrict__ ip = in + plane * Hl * Wl;
+
+    phase_twiddles(tw, N);
+    for (int t = 0; t < T; ++t) {
+        const int i = i0 + t;
+        for (int q = threadIdx.x; q < N; q += kBlock) {
+            float val = 0.f;
+            if (i < Hl && (q & (g.s - 1)) == 0) {
+                SP_DCHECK((q >> sh) < Wl && i * Wl + (q >> sh) < Hl * Wl);
+                val = ip[i * Wl + (q >> sh)];
+            }
+            A[t * NP + phase_slot(q)] = make_float2(val, 0.f);
+        }
+    }
+    __syncthreads();
+    const float2* res = phase_fft(A, B, tw, N, NP, T, false);
+    float2* __restrict__ wp = ws + plane * (int64_t)g.HW * g.H;
+    const int total = T * g.HW;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, i = i0 + t;
+        if (i < Hl) {
+            SP_DCHECK(kw < g.HW && kw * g.H + i < g.HW * g.H);
+            wp[kw * g.H + i] = res[t * NP + phase_slot(kw)];
+        }
+    }
+}
+
+// launch 3 of the down maps on the H / s lattice rows at [kw][i].  RESIDUAL false: inverse FFT, the
+// W / s lattice columns -> out.  True, the fused launch: g = gs (y - A x0) on the lattice and the
+// r^2 partial of the tile (partial null: not stored), g zero-inserted along the row, forward FFT
+// back to [kw][i].  y rows are y_stride floats apart.
+template <bool RESIDUAL>
+__global__ __launch_bounds__(kBlock) void k_srp_rows_inv(pf_geom g, float2* __restrict__ ws,
+                                                         float* __restrict__ out,
+                                                         const float* __restrict__ y, int64_t y_stride,
+                                                         int64_t y_div, float gs,
+                                                         float* __restrict__ partial, int P, int T,
+                                                         const sp_step_rec* __restrict__ sched,
+                                                         const int32_t* __restrict__ cursor) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[4];
+    if (RESIDUAL && sched) gs = sched[*cursor].c.grad_scale;
+    const int N = g.W, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int sh = __ffs(g.s) - 1, Hl = g.H >> sh, Wl = g.W >> sh;
+    const int tiles = (Hl + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int i0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t b = blockIdx.y;
+    const int64_t plane = b * g.C + c;
+    SP_DCHECK(c < g.C && i0 < Hl && N == g.Nw && g.s == (1 << sh) &&
+              (!RESIDUAL || static_cast<int>(blockIdx.x) < P));
+    float2* __restrict__ wp = ws + plane * (int64_t)g.HW * g.H;
+
+    phase_twiddles(tw, N);
+    const int total = T * g.HW;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, i = i0 + t;
+        float2 val = make_float2(0.f, 0.f);
+        if (i < Hl) {
+            SP_DCHECK(kw < g.HW && kw * g.H + i < g.HW * g.H);
+            val = wp[kw * g.H + i];
+        }
+        A[t * NP + phase_slot(kw)] = val;
+        if (kw > 0 && 2 * kw < N) {  // the spectrum of a real row: X[N - kw] = conj(X[kw])
+            SP_DCHECK(N - kw >= g.HW && N - kw < N);
+            A[t * NP + phase_slot(N - kw)] = make_float2(val.x, -val.y);
+        }
+    }
+    __syncthreads();
+    float2* res = phase_fft(A, B, tw, N, NP, T, true);
+
+    if constexpr (RESIDUAL) {
+        const float* __restrict__ yp = y + (b / y_div) * y_stride + (int64_t)c * Hl * Wl;
+        float racc = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const int i = i0 + t;
+            // every element is read and rewritten by the one thread that owns it
+            for (int q = threadIdx.x; q < N; q += kBlock) {
+                float gv = 0.f;
+                float2* rp = res + t * NP + phase_slot(q);
+                if (i < Hl && (q & (g.s - 1)) == 0) {
+                    SP_DCHECK((q >> sh) < Wl && i * Wl + (q >> sh) < Hl * Wl);
+                    const float r = yp[i * Wl + (q >> sh)] - rp->x;
+                    racc += r * r;
+                    gv = gs * r;
+                }
+                *rp = make_float2(gv, 0.f);
+            }
+        }
+        const float tsum = block_sum(racc, red);  // its barrier also orders the rewritten rows
+        if (partial && threadIdx.x == 0) partial[b * P + blockIdx.x] = tsum;
+        __syncthreads();
+        const float2* f = phase_fft(res, res == A ? B : A, tw, N, NP, T, false);
+        for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int kw = idx / T, t = idx - kw * T, i = i0 + t;
+            if (i < Hl) {
+                SP_DCHECK(kw < g.HW && kw * g.H + i < g.HW * g.H);
+                wp[kw * g.H + i] = f[t * NP + phase_slot(kw)];
+            }
+        }
+    } else {
+        float* __restrict__ op_out = out + plane * Hl * Wl;
+        for (int t = 0; t < T; ++t) {
+            const int i = i0 + t;
+            if (i >= Hl) break;
+            const float2* rl = res + t * NP;
+            for (int j = threadIdx.x; j < Wl; j += kBlock) {
+                SP_DCHECK(i * Wl + j < Hl * Wl && (j << sh) < N);
+                op_out[i * Wl + j] = rl[phase_slot(j << sh)].x;
+            }
+        }
+    }
+}
+
+// q of the prepares: row r of y (m floats) to q + r * stride
+__global__ __launch_bounds__(kBlock) void k_srp_stash(const float* __restrict__ y,
+                                                      float* __restrict__ q, int64_t m,
+                                                      int64_t stride) {
+    const int64_t r = blockIdx.y;
+    SP_DCHECK(m <= stride);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock)
+        q[r * stride + i] = y[r * m + i];
 }
 
 // ---------------------------------------------------------------------------
@@ -445,6 +682,9 @@ static pf_geom pf_geometry(const sp_op* op, int which = PP_SPEC_M) {
     g.Nw = ext ? pf_size(op->width + 2 * op->radius) : op->width;
     g.HW = g.Nw / 2 + 1;
     g.spec = reinterpret_cast<const float2*>(op->taps) + (int64_t)which * g.HW * g.Nh;
+    const bool srp = op->kind == SP_OP_SR_PERIODIC;  // M, P, then Lambda_t
+    g.s = srp ? op->factor : 1;
+    g.lam = srp ? op->taps + 4 * (int64_t)g.HW * g.Nh : nullptr;
     return g;
 }
 
@@ -528,9 +768,10 @@ static int pf_rows_inv(const pf_run& p, bool adj, float* out) {
 }
 
 // launch 3 of the proximal map: ws -> z, or the DiffPIR sample formed from z in the epilogue
-static int pf_rows_prox(const pf_run& p, float* out, const pf_prox_tail& px) {
+static int pf_rows_prox(const pf_run& p, float* out, const pf_prox_tail& px, bool add_x0 = false) {
     const pf_geom& g = p.g;
-    return fft_stage(p.what, p.kind, 0.0, k_pf_rows_inv<PF_OUT_PROX>, g.C * pf_row_tiles(g), p.batch,
+    const auto kern = add_x0 ? k_pf_rows_inv<PF_OUT_PROX_ADD> : k_pf_rows_inv<PF_OUT_PROX>;
+    return fft_stage(p.what, p.kind, 0.0, kern, g.C * pf_row_tiles(g), p.batch,
                      g.Nw, p.s, g, p.ws, out, kNoIn, (int64_t)1, 0.f, kNoOut, 0, phase_lines(g.Nw),
                      kNoSched, kNoCursor, px);
 }
@@ -627,7 +868,162 @@ int psf_periodic_prox(const sp_op* op, const prox_args& a, hipStream_t s) {
     if (rc == SP_OK)
         rc = pf_cols(p, false, PF_COL_PROX, reinterpret_cast<const float2*>(a.q), a.y_div, a.c.rho);
     if (rc == SP_OK)
-        rc = pf_rows_prox(p, a.out, {a.x, a.xi, a.seed, a.step, a.sample_offset, a.c, a.eps != nullptr});
+        rc = pf_rows_prox(p, a.out,
+                          {a.x, a.xi, nullptr, a.seed, a.step, a.sample_offset, a.c, a.eps != nullptr});
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// SP_OP_SR_PERIODIC, host side
+// ---------------------------------------------------------------------------
+// radius = K taps per axis, factor = s, taps = M, P (half spectra) then Lambda_t
+bool sr_periodic_valid(const sp_op* op) {
+    const int s = op->factor;
+    if (!op->taps || op->keep_bits || op->word_rank || (s != 2 && s != 4 && s != 8) ||
+        op->channels <= 0 || !phase_size_ok(op->height) || !phase_size_ok(op->width) ||
+        op->height % s || op->width % s || op->radius < s ||
+        op->radius > std::min(op->height, op->width) || (op->radius - s) % 2)
+        return false;
+    return (int64_t)op->channels * op->height * op->width == op->n && op->m * s * s == op->n;
+}
+
+// lattice rows per workgroup of the launches that transform the H / s lattice rows alone
+static inline int srp_lines(const pf_geom& g) { return std::min(phase_lines(g.W), g.H / g.s); }
+static inline int srp_tiles(const pf_geom& g) {
+    const int T = srp_lines(g);
+    return (g.H / g.s + T - 1) / T;
+}
+
+// lattice-row tiles per sample = workgroups per sample of the fused launch = r^2 partials
+int64_t sr_periodic_partials(const sp_op* op) {
+    return (int64_t)op->channels * srp_tiles(pf_geometry(op));
+}
+
+// launch 2: down (A, A^+T) or up (A^T, A^+, prox) with p's spectrum, conjugated or not
+static int srp_cols(const pf_run& p, bool up, bool conj, bool prox = false, float rho = 0.f) {
+    const pf_geom& g = p.g;
+    const auto kern = prox ? k_srp_cols<true, true> : up ? k_srp_cols<true, false> : k_srp_cols<false, false>;
+    return fft_stage(p.what, p.kind, 0.0, kern, g.C * pf_col_tiles(g), p.batch, g.H, p.s, g, p.ws,
+                     phase_lines(g.H), conj ? -1.f : 1.f, rho);
+}
+
+static int srp_rows_up(const pf_run& p, const float* in) {
+    const pf_geom& g = p.g;
+    return fft_stage(p.what, p.kind, p.kind ? (double)p.batch : 0.0, k_srp_rows_up, g.C * srp_tiles(g),
+                     p.batch, g.W, p.s, g, in, p.ws, srp_lines(g));
+}
+
+static int srp_rows_inv(const pf_run& p, float* out) {
+    const pf_geom& g = p.g;
+    return fft_stage(p.what, p.kind, 0.0, k_srp_rows_inv<false>, g.C * srp_tiles(g), p.batch, g.W, p.s,
+                     g, p.ws, out, kNoIn, (int64_t)0, (int64_t)1, 0.f, kNoOut, 0, srp_lines(g), kNoSched,
+                     kNoCursor);
+}
+
+// the fused middle launch: y rows `y_stride` floats apart; partial may be null (PGDM, prox)
+static int srp_rows_residual(const pf_run& p, const float* y, int64_t y_stride, int64_t y_div, float gs,
+                             float* partial, const sp_step_rec* sched, const int32_t* cursor) {
+    const pf_geom& g = p.g;
+    const int P = g.C * srp_tiles(g);
+    return fft_stage(p.what, p.kind, 0.0, k_srp_rows_inv<true>, P, p.batch, g.W, p.s, g, p.ws, kNoOut,
+                     y, y_stride, y_div, gs, partial, P, srp_lines(g), sched, cursor);
+}
+
+int sr_periodic_apply(const sp_op* op, const float* x, float* y, int64_t batch, float* work,
+                      hipStream_t s) {
+    const pf_run p = pf_begin("sp_op_apply_ws", 0, op, PP_SPEC_M, batch, work, s);
+    int rc = pf_rows(p, false, x);
+    if (rc == SP_OK) rc = srp_cols(p, false, false);
+    if (rc == SP_OK) rc = srp_rows_inv(p, y);
+    return rc;
+}
+
+int sr_periodic_vjp(const sp_op* op, const float* x, const float* gy, float* dx, int64_t batch,
+                    float* work, hipStream_t s) {
+    (void)x;
+    const pf_run p = pf_begin("sp_op_vjp_ws", 0, op, PP_SPEC_M, batch, work, s);
+    int rc = srp_rows_up(p, gy);
+    if (rc == SP_OK) rc = srp_cols(p, true, true);
+    if (rc == SP_OK) rc = pf_rows_inv(p, false, dx);
+    return rc;
+}
+
+// A^+ (up, P) or its transpose (down, conj(P))
+int sr_periodic_pinv(const sp_op* op, const float* y, float* x, int64_t batch, int transpose,
+                     float* work, hipStream_t s) {
+    const pf_run p = pf_begin("sp_op_pinv_ws", 0, op, PP_SPEC_P, batch, work, s);
+    int rc = transpose ? pf_rows(p, false, y) : srp_rows_up(p, y);
+    if (rc == SP_OK) rc = srp_cols(p, !transpose, transpose != 0);
+    if (rc == SP_OK) rc = transpose ? srp_rows_inv(p, x) : pf_rows_inv(p, false, x);
+    return rc;
+}
+
+// the first three launches of every fused pass: x0 -> A x0 on the lattice -> FFT rows of
+// up(gs (y - A x0)) in the intermediate
+static int srp_residual_head(const pf_run& p, const float* x, const pf_x0* x0, const float* y,
+                             int64_t y_stride, int64_t y_div, float gs, float* partial,
+                             const sp_step_rec* sched, const int32_t* cursor) {
+    int rc = pf_rows(p, false, x, x0);
+    if (rc == SP_OK) rc = srp_cols(p, false, false);
+    if (rc == SP_OK) rc = srp_rows_residual(p, y, y_stride, y_div, gs, partial, sched, cursor);
+    return rc;
+}
+
+int sr_periodic_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
+    const pf_run p =
+        pf_begin("sp_dps_residual_ws", TK_DPS_RESIDUAL, op, PP_SPEC_M, r.batch, r.work, s);
+    const pf_x0 x0 = {r.eps, r.a, r.k, r.sched, r.cursor};
+    int rc = srp_residual_head(p, r.x, &x0, r.y, op->m, r.y_div, r.gs, r.partial, r.sched, r.cursor);
+    if (rc == SP_OK) rc = srp_cols(p, true, true);
+    if (rc == SP_OK) rc = pf_rows_inv(p, false, r.v);
+    return rc;
+}
+
+// q of both prepares: y itself, one row per observation at the intermediate's per-sample stride
+// (the callers size and slice q by sp_op_workspace(op, 1)).  The fused passes subtract A x0 on
+// the lattice, where y is m floats a row; a spectrum of up(y) would be 2 s^2 times that to read.
+static int srp_stash(const char* what, const sp_op* op, const float* y, int64_t rows, float* q,
+                     hipStream_t s) {
+    launch(0, k_srp_stash, dim3((unsigned)std::min<int64_t>(cdiv(op->m, kBlock), 1024), (unsigned)rows),
+           dim3(kBlock), s, y, q, op->m, psf_fft_workspace(op, 1));
+    return check_launch(what);
+}
+
+int sr_periodic_pgdm_prepare(const sp_op* op, const float* y, int64_t rows, float* q, hipStream_t s) {
+    return srp_stash("sp_pgdm_prepare", op, y, rows, q, s);
+}
+
+int sr_periodic_prox_prepare(const sp_op* op, const float* y, int64_t rows, float* q, hipStream_t s) {
+    return srp_stash("sp_prox_prepare", op, y, rows, q, s);
+}
+
+// v = gs A^+ (y - A x0): the DPS sequence with P in the second column launch
+int sr_periodic_pgdm_residual(const sp_op* op, const float* x, const float* eps, const float* q,
+                              int64_t batch, int64_t y_div, const sp_dps_coefs& c, float* v,
+                              float* work, hipStream_t s) {
+    const pf_run pm = pf_begin("sp_pgdm_residual_ws", TK_DPS_RESIDUAL, op, PP_SPEC_M, batch, work, s);
+    const pf_run pp = pf_begin("sp_pgdm_residual_ws", TK_DPS_RESIDUAL, op, PP_SPEC_P, batch, work, s);
+    const pf_x0 x0 = {eps, c.a, c.k, kNoSched, kNoCursor};
+    int rc = srp_residual_head(pm, x, &x0, q, psf_fft_workspace(op, 1), y_div, c.grad_scale, kNoOut,
+                               kNoSched, kNoCursor);
+    if (rc == SP_OK) rc = srp_cols(pp, true, false);
+    if (rc == SP_OK) rc = pf_rows_inv(pp, false, v);
+    return rc;
+}
+
+// z = x0 + A^T (A A^T + rho)^-1 (y - A x0): the DPS sequence with conj(M) / (Lambda_t + rho) in
+// the second column launch (every frequency divided), x0 added by the epilogue
+int sr_periodic_prox(const sp_op* op, const prox_args& a, hipStream_t s) {
+    const pf_run p = pf_begin(a.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws", 0, op, PP_SPEC_M,
+                              a.batch, a.work, s);
+    const pf_x0 x0 = {a.eps, a.c.a, a.c.k, kNoSched, kNoCursor};
+    int rc = srp_residual_head(p, a.x, a.eps ? &x0 : nullptr, a.q, psf_fft_workspace(op, 1), a.y_div,
+                               1.f, kNoOut, kNoSched, kNoCursor);
+    if (rc == SP_OK) rc = srp_cols(p, true, true, true, a.c.rho);
+    if (rc == SP_OK)
+        rc = pf_rows_prox(p, a.out,
+                          {a.x, a.xi, a.eps, a.seed, a.step, a.sample_offset, a.c, a.eps != nullptr},
+                          true);
     return rc;
 }
 

@@ -18,6 +18,7 @@ from .periodic import PeriodicBlurOperator, pseudo_inverse_spectrum, transfer_fu
 from .psf_fft import FFTPSFBlurOperator, padded_size, psf_spectrum
 from .radon import RadonOperator, radon_table
 from .sr_filter import BicubicSuperResolutionOperator, FilteredSuperResolutionOperator, bicubic_taps
+from .sr_periodic import PeriodicSuperResolutionOperator
 from .superres import SuperResolutionOperator
 
 __all__ = [
@@ -36,6 +37,7 @@ __all__ = [
     "SuperResolutionOperator",
     "FilteredSuperResolutionOperator",
     "BicubicSuperResolutionOperator",
+    "PeriodicSuperResolutionOperator",
     "bicubic_taps",
     "PSFBlurOperator",
     "MotionBlurOperator",

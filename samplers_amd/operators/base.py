@@ -137,7 +137,7 @@ def _work(lib, desc, batch: int, like: Tensor) -> Tensor:
 
 
 class HipWorkspaceMap(torch.autograd.Function):
-    """A linear map with ``y_shape == x_shape`` that runs through a workspace:
+    """A linear map that runs through a workspace:
     ``forward(op, t, pinv, transpose)`` is ``sp_op_apply_ws`` (A), ``sp_op_vjp_ws`` (Aᵀ) or
     ``sp_op_pinv_ws`` (A⁺, A⁺ᵀ); the backward of a linear map is its transpose, so it
     differentiates to any order."""
@@ -158,9 +158,13 @@ def _hip_workspace_map(op: Operator, t: Tensor, pinv: bool, transpose: bool) -> 
     if t.dtype != torch.float32:
         raise _hip.HipLibraryError(f"{type(op).__name__}: HIP operators compute in fp32")
     lib, desc = _hip.load_library(), op.hip_descriptor()
-    flat, batch = _flatten_batch(t.detach(), op.x_shape)
-    out = torch.empty_like(flat)
+    # A and A^+T take x_shape to y_shape, A^T and A^+ the other way (the same shape but for the
+    # periodic super-resolution operator)
+    in_shape, out_shape = ((op.x_shape, op.y_shape) if pinv == transpose
+                           else (op.y_shape, op.x_shape))
+    flat, batch = _flatten_batch(t.detach(), in_shape)
     n = flat.shape[0]
+    out = torch.empty((n, *out_shape), device=flat.device, dtype=torch.float32)
     if n > 0:
         work, stream = _work(lib, desc, n, flat), _hip.stream_of(t)
         if pinv:
@@ -172,7 +176,7 @@ def _hip_workspace_map(op: Operator, t: Tensor, pinv: bool, transpose: bool) -> 
         else:
             _hip.check(lib.sp_op_apply_ws(desc, _hip.ptr(flat), _hip.ptr(out), n, _hip.ptr(work),
                                           stream), "sp_op_apply_ws")
-    return out.reshape(*batch, *op.x_shape)
+    return out.reshape(*batch, *out_shape)
 
 
 def check_rho(rho: float) -> float:

@@ -14,7 +14,8 @@ with ``x0 = (x − k·eps)/a``, ``z = argmin_u ‖y − A u‖² + ρ_t ‖u −
 differentiated, which is where the step's time goes in DPS and PGDM.
 
 Only the operators whose proximal map has a closed form run (``Operator.apply_prox``: identity,
-inpainting / mask, ×s super-resolution, periodic blur); the others raise ``NotImplementedError``.
+inpainting / mask, ×s super-resolution, periodic blur, periodic blur-and-decimate
+super-resolution); the others raise ``NotImplementedError``.
 The noise model must be ``GaussianNoise``: σ_n enters ρ_t.  The step runs eagerly (no graph
 replay form).  Noise sources (``rng`` / ``seed`` / ``noise_fn``) are ``DPSSampler``'s.
 """
@@ -49,7 +50,8 @@ def prox_descriptor(operator) -> "_hip.SpOp":
         raise NotImplementedError(
             f"{type(operator).__name__} has no closed-form proximal map (apply_prox): DiffPIR "
             "supports IdentityOperator, InpaintingOperator (and subclasses), "
-            "SuperResolutionOperator and PeriodicBlurOperator")
+            "SuperResolutionOperator, PeriodicBlurOperator and "
+            "PeriodicSuperResolutionOperator")
     return desc
 
 

@@ -131,7 +131,8 @@ class FusedDPSStep:
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
                 "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses), "
-                "FFTPSFBlurOperator, PeriodicBlurOperator, RadonOperator and PhaseRetrievalOperator"
+                "FFTPSFBlurOperator, PeriodicBlurOperator, PeriodicSuperResolutionOperator, "
+                "RadonOperator and PhaseRetrievalOperator"
             )
         _hip.require_cuda(observation_rows, "DPSSampler")
         if observation_rows.dtype != torch.float32:

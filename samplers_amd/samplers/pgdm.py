@@ -8,6 +8,7 @@ prior's input-VJP gives w = Jᵀv, and pass 2 writes
 ``ddim_step(x, x0) − guidance_weight·sqrt(1−ᾱ_t)·(v − k w)/a``.
 ``PeriodicBlurOperator`` has a pseudo-inverse of its own (a per-frequency division): its pass 1
 is ``sp_pgdm_residual_ws``, v = −2 (A⁺y − A⁺A x0), over Q = P ⊙ FFT2(y) prepared once per call.
+``PeriodicSuperResolutionOperator`` likewise (v = −2 A⁺(y − A x0), q holding y itself).
 Operators without ``apply_pseudo_inverse`` raise ``NotImplementedError`` as in
 the reference (``pgdm.py:56-66``).
 """

@@ -1,0 +1,624 @@
+"""Periodic blur-and-decimate super-resolution (SP_OP_SR_PERIODIC, csrc/sp_psf_fft.hip) on the GPU
+through the raw entry points, NaN-filled outputs between guard bands: the four maps, DPS pass 1,
+the fused PGDM pass 1, the proximal map and the DiffPIR step against the fp64 reference of
+tests/sr_periodic_ops.py (its spectral route, which tests/test_sr_periodic_ops.py pins to dense
+matrices), the fused passes against their compositions, the map against SP_OP_SR and
+SP_OP_PSF_PERIODIC, the bitwise properties, autograd, and the four samplers against their oracle
+loops.
+
+Bounds: 2e-5 x max|ref| for the maps and passes (the periodic / PSF-FFT suites' bound), 2e-5
+relative on ||r||^2; max(2e-5, 4 x the fp32 torch.fft evaluation's own distance to fp64) x max|ref|
+for prox and the DiffPIR step (the DiffPIR suite's); 1e-4 relative L2 for the DPS, PSLD and DiffPIR
+trajectories; max(1e-4, 20 x the fp32 oracle loop's distance to fp64) for PGDM.  Every measured
+figure goes through parity_record.
+
+Largest errors measured on an MI355X over CASES: A 2.3e-7, A^T 2.3e-7, A^+ 2.4e-7, A^+T 2.5e-7,
+pass-1 v 3.5e-7 (all x max|ref|), ||r||^2 2.7e-7 relative, PGDM v 3.7e-7, the fused passes bit for
+bit their compositions, prox z 2.5e-7 and DiffPIR x' 2.9e-7 (the torch.fft yardstick 2.6e-7, so
+the bound in force was 2e-5), 1.9e-7 against SP_OP_SR, 6.2e-8 against the lattice of
+SP_OP_PSF_PERIODIC; trajectories bicubic / Gaussian: DPS 3.3e-7 / 3.0e-7, DiffPIR 2.6e-7 / 2.7e-7,
+PSLD 3.7e-7 / 4.5e-7, PGDM 6.9e-4 / 9.9e-3 under 2.5e-2 / 2.2e-1."""
+
+import math
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+import torch
+
+import exact_cases as ec
+import prox_ref as pr
+import sr_periodic_ops as so
+import stand_ins as si
+from oracle import dps_loop
+from oracle.latent_loops import pgdm_reference, psld_reference
+from samplers_amd import _hip
+from samplers_amd.inverse_problem import InverseProblem
+from samplers_amd.noise import GaussianNoise
+from samplers_amd.operators import (PeriodicBlurOperator, PeriodicSuperResolutionOperator,
+                                    SuperResolutionOperator, bicubic_taps)
+from samplers_amd.operators.sr_filter import gaussian_filter_taps
+from samplers_amd.samplers import DPSSampler
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+BOUND = 2e-5
+SEED, STEP, OFFSET = 1234, 5, 3
+
+
+def _rand2d():
+    return torch.randn(4, 4, generator=torch.Generator().manual_seed(77)) / 4
+
+
+# shape (C, H, W), s, taps, kept / all (None: not pinned): the smallest that reach each path
+CASES = [
+    ((1, 8, 8), 2, lambda: torch.full((2,), 0.5), None),            # box, K = 2: the smallest valid
+    ((1, 8, 8), 2, lambda: bicubic_taps(2), None),                  # K = min(H, W): every tap wraps
+    ((1, 8, 8), 2, lambda: so.ASYM, (16, 16)),                      # asymmetric
+    ((2, 16, 24), 2, lambda: bicubic_taps(2), (96, 96)),            # 3 * 2^k width
+    ((3, 32, 16), 4, lambda: bicubic_taps(4), (32, 32)),            # K = W
+    ((1, 32, 32), 4, lambda: gaussian_filter_taps(16, 3.0), (59, 64)),   # drops 5 of 64
+    ((1, 32, 64), 8, lambda: gaussian_filter_taps(32, 6.0), (29, 32)),   # drops 3 of 32
+    ((1, 16, 16), 8, lambda: bicubic_taps(8)[8:24], (4, 4)),        # 2 x 2 lattice
+    ((1, 48, 96), 8, lambda: bicubic_taps(8), None),                # K = 32
+    ((1, 16, 16), 2, _rand2d, None),                                # 2-D, non-separable
+    ((1, 512, 1024), 4, lambda: bicubic_taps(4), None),             # batch 1, the largest transforms
+]
+IDS = [f"{'x'.join(map(str, c[0]))}-s{c[1]}-{i}" for i, c in enumerate(CASES)]
+BATCHES = [(3, 3), (4, 2)]
+BIG = len(CASES) - 1
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _batches(i, batch, ydiv):
+    return (1, 1) if i == BIG else (batch, ydiv)
+
+
+_CACHE = {}
+
+
+class Case:
+    """One shape at one batching: the host operator, inputs and fp64 references, computed once,
+    shared and never modified."""
+
+    def __init__(self, i, batch, ydiv):
+        shape, s, make, kept = CASES[i]
+        self.shape, self.s, self.batch, self.ydiv = shape, s, batch, ydiv
+        self.taps = make()
+        self.host = PeriodicSuperResolutionOperator(shape, self.taps, factor=s)
+        if kept is not None:
+            assert (int(self.host.keep.sum()), self.host.keep.numel()) == kept
+        c, H, W = shape
+        self.yshape = (c, H // s, W // s)
+        self.n, self.m = math.prod(shape), math.prod(self.yshape)
+        self.ref = so.Ref(self.taps, H, W, s, self.host.keep)
+        g = torch.Generator().manual_seed(40 + i)
+        self.x, self.eps, self.xi = (torch.randn(batch, *shape, generator=g) for _ in range(3))
+        self.cot = torch.randn(batch, *self.yshape, generator=g)
+        self.y = torch.randn(batch // ydiv, *self.yshape, generator=g)
+        self.rows = self.y.repeat_interleave(ydiv, dim=0)
+        self._dev = None
+
+    def dev(self, cuda):
+        if self._dev is None:
+            op = PeriodicSuperResolutionOperator(self.shape, self.taps, factor=self.s).to(cuda)
+            self._dev = (op, op.hip_descriptor())
+        return self._dev
+
+
+def _case(i, batch, ydiv) -> Case:
+    batch, ydiv = _batches(i, batch, ydiv)
+    key = (i, batch, ydiv)
+    if key not in _CACHE:
+        _CACHE[key] = Case(i, batch, ydiv)
+    return _CACHE[key]
+
+
+def _err(got, ref):
+    return float((got.detach().cpu().double().reshape(ref.shape) - ref).abs().max() / ref.abs().max())
+
+
+def _close(got, ref, what, record, bound=BOUND, **extra):
+    err = _err(got, ref)
+    print(f"{what}: max err / max|ref| = {err:.3g} (bound {bound:.3g})")
+    record(what, err, bound, **extra)
+    assert err <= bound, (what, err, bound)
+
+
+class Run:
+    """The raw entry points on one descriptor, every output NaN-filled between guard bands."""
+
+    def __init__(self, cuda, desc, n, m):
+        self.lib, self.dev, self.desc, self.n, self.m = _hip.load_library(), cuda, desc, n, m
+        self.per_sample = int(self.lib.sp_op_workspace(desc, 1))
+
+    def work(self, batch):
+        floats = int(self.lib.sp_op_workspace(self.desc, batch))
+        assert floats == batch * self.per_sample
+        return ec.Guarded((floats,), 64, self.dev)
+
+    def _map(self, fn, t, out_elems, *mid):
+        batch = t.shape[0]
+        work, out = self.work(batch), ec.Guarded((batch, out_elems), 64, self.dev)
+        _hip.check(fn(self.desc, *[a.data_ptr() for a in mid], t.data_ptr(), out.ptr(), batch,
+                      *self._tail, work.ptr(), _stream()), "map")
+        work.check(nan_ok=True)
+        return out.check()
+
+    def apply(self, x):
+        self._tail = ()
+        return self._map(self.lib.sp_op_apply_ws, x, self.m)
+
+    def adjoint(self, y):
+        self._tail = ()
+        return self._map(self.lib.sp_op_vjp_ws, y, self.n, y)  # the x argument is not read
+
+    def pinv(self, t, transpose):
+        self._tail = (int(transpose),)
+        return self._map(self.lib.sp_op_pinv_ws, t, self.m if transpose else self.n)
+
+    def partials(self):
+        return int(self.lib.sp_rsq_partials(self.desc))
+
+    def residual(self, x, eps, y, ydiv, coefs, sched=None):
+        batch, P = x.shape[0], self.partials()
+        work, v = self.work(batch), ec.Guarded((batch, self.n), 64, self.dev)
+        part = ec.Guarded((batch, P), 64, self.dev)
+        if sched is None:
+            rc = self.lib.sp_dps_residual_ws(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(),
+                                             batch, ydiv, coefs, v.ptr(), part.ptr(), work.ptr(),
+                                             _stream())
+        else:
+            rc = self.lib.sp_dps_residual_sched_ws(self.desc, x.data_ptr(), eps.data_ptr(),
+                                                   y.data_ptr(), batch, ydiv, sched[0].data_ptr(),
+                                                   sched[1].data_ptr(), v.ptr(), part.ptr(),
+                                                   work.ptr(), _stream())
+        _hip.check(rc, "sp_dps_residual_ws")
+        work.check(nan_ok=True)
+        return v.check(), part.check()
+
+    def prepare(self, y, prox):
+        """q: one row of sp_op_workspace(1) floats per observation row."""
+        rows = y.shape[0]
+        size = int(self.lib.sp_prox_prepare_size(self.desc, rows))
+        assert size == rows * self.per_sample == int(self.lib.sp_op_workspace(self.desc, rows))
+        q = ec.Guarded((rows, self.per_sample), 64, self.dev)
+        fn = self.lib.sp_prox_prepare if prox else self.lib.sp_pgdm_prepare
+        _hip.check(fn(self.desc, y.data_ptr(), rows, q.ptr(), _stream()), "prepare")
+        return q.check(nan_ok=True)
+
+    def pgdm(self, x, eps, q, ydiv, coefs):
+        batch = x.shape[0]
+        work, v = self.work(batch), ec.Guarded((batch, self.n), 64, self.dev)
+        _hip.check(self.lib.sp_pgdm_residual_ws(self.desc, x.data_ptr(), eps.data_ptr(), q.data_ptr(),
+                                                batch, ydiv, coefs, v.ptr(), work.ptr(), _stream()),
+                   "sp_pgdm_residual_ws")
+        work.check(nan_ok=True)
+        return v.check()
+
+    def prox(self, x0, q, ydiv, rho):
+        batch = x0.shape[0]
+        work, out = self.work(batch), ec.Guarded((batch, self.n), 64, self.dev)
+        _hip.check(self.lib.sp_op_prox_ws(self.desc, x0.data_ptr(), None, q.data_ptr(), batch, ydiv,
+                                          rho, out.ptr(), work.ptr(), _stream()), "sp_op_prox_ws")
+        work.check(nan_ok=True)
+        return out.check()
+
+    def step(self, x, eps, q, xi, ydiv, coefs, alias=False, offset=OFFSET):
+        batch = x.shape[0]
+        work, out = self.work(batch), ec.Guarded((batch, self.n), 64, self.dev)
+        if alias:
+            out.t.copy_(x)
+        src = out.t if alias else x
+        _hip.check(self.lib.sp_diffpir_step_ws(self.desc, src.data_ptr(), eps.data_ptr(), None,
+                                               q.data_ptr(), xi.data_ptr() if xi is not None else None,
+                                               SEED, STEP, offset, batch, ydiv, coefs, out.ptr(),
+                                               work.ptr(), _stream()), "sp_diffpir_step_ws")
+        work.check(nan_ok=True)
+        return out.check()
+
+
+def _flat(cuda, *ts):
+    return [t.reshape(t.shape[0], -1).to(cuda).contiguous() for t in ts]
+
+
+def _params(fn):
+    fn = pytest.mark.parametrize("batch,ydiv", BATCHES, ids=["b3d3", "b4d2"])(fn)
+    return pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)(fn)
+
+
+@_params
+def test_four_maps(cuda, parity_record, i, batch, ydiv):
+    c = _case(i, batch, ydiv)
+    op, desc = c.dev(cuda)
+    run = Run(cuda, desc, c.n, c.m)
+    xd, cd = _flat(cuda, c.x, c.cot)
+    ax, atc, pc, ptx = run.apply(xd), run.adjoint(cd), run.pinv(cd, 0), run.pinv(xd, 1)
+    _close(ax, c.ref.A(c.x), "apply_max_err_over_max", parity_record)
+    _close(atc, c.ref.At(c.cot), "adjoint_max_err_over_max", parity_record)
+    _close(pc, c.ref.pinv(c.cot), "pinv_max_err_over_max", parity_record)
+    _close(ptx, c.ref.pinv_t(c.x), "pinv_transpose_max_err_over_max", parity_record)
+    # the same call twice, and a sample alone: the same bits
+    assert torch.equal(run.apply(xd), ax) and torch.equal(run.adjoint(cd), atc)
+    assert torch.equal(run.apply(xd[-1:]), ax[-1:]) and torch.equal(run.adjoint(cd[-1:]), atc[-1:])
+    assert torch.equal(run.pinv(cd[-1:], 0), pc[-1:]) and torch.equal(run.pinv(xd[-1:], 1), ptx[-1:])
+    # autograd of the four maps through the operator: each backward is its transpose, the same bits
+    x4, c4 = xd.reshape(c.batch, *c.shape), cd.reshape(c.batch, *c.yshape)
+    assert torch.equal(op.apply(x4).reshape(ax.shape), ax)
+    xr = x4.clone().requires_grad_()
+    (gx,) = torch.autograd.grad(op.apply(xr), xr, grad_outputs=c4)
+    assert torch.equal(gx.reshape(atc.shape), atc)
+    cr = c4.clone().requires_grad_()
+    (gc,) = torch.autograd.grad(op.apply_transpose(cr), cr, grad_outputs=x4)
+    assert torch.equal(gc.reshape(ax.shape), ax)
+    cr = c4.clone().requires_grad_()
+    (gp,) = torch.autograd.grad(op.apply_pseudo_inverse(cr), cr, grad_outputs=x4)
+    assert torch.equal(gp.reshape(ptx.shape), ptx)
+    xr, cr = x4.clone().requires_grad_(), c4.clone().requires_grad_()
+    (inner,) = torch.autograd.grad(op.apply_pseudo_inverse(cr), cr, grad_outputs=xr, create_graph=True)
+    (back,) = torch.autograd.grad(inner, xr, grad_outputs=c4)
+    assert torch.equal(back.reshape(pc.shape), pc)
+    # <A x, y> = <x, A^T y> to fp32 accuracy
+    lhs = float((ax.double() * cd.double()).sum())
+    rhs = float((xd.double() * atc.double()).sum())
+    assert abs(lhs - rhs) <= 2e-5 * float(ax.double().norm() * cd.double().norm())
+
+
+def _sched_of(coefs, cuda):
+    recs = (_hip.SpStepRec * 2)()
+    recs[0].c, recs[0].step, recs[0].t = _hip.SpDpsCoefs(0.9, 0.4, 7.0, 0.1, 0.9, 0.6, 0.5, 1e-3), 99, 1
+    recs[1].c, recs[1].step, recs[1].t = coefs, 3, 5
+    sched = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(cuda)
+    return sched, torch.ones(1, dtype=torch.int32, device=cuda)
+
+
+def _lines(N):
+    NP = (N + N // 16) | 1
+    return max(1, min(16, (32000 - 8 * N) // (16 * NP)))
+
+
+@_params
+def test_dps_pass_1(cuda, parity_record, i, batch, ydiv):
+    """v = gs A^T (y - A x0) and the ||r||^2 partials, x0 = (x - k eps) / a."""
+    c = _case(i, batch, ydiv)
+    op, desc = c.dev(cuda)
+    run = Run(cuda, desc, c.n, c.m)
+    a, k, gs = 0.3, math.sqrt(1 - 0.09), 400.0
+    coefs = _hip.SpDpsCoefs(a, k, gs, 0.9, 0.2, 0.1, 0.05, 1e-9)
+    hl = c.shape[1] // c.s
+    t = min(_lines(c.shape[2]), hl)
+    assert run.partials() == c.shape[0] * -(-hl // t)  # one partial per (plane, lattice-row tile)
+    xd, ed, yd = _flat(cuda, c.x, c.eps, c.y)
+    v, part = run.residual(xd, ed, yd, c.ydiv, coefs)
+    x0 = (c.x.double() - k * c.eps.double()) / a
+    r = c.rows.double() - c.ref.A(x0)
+    _close(v, gs * c.ref.At(r), "pass1_v_max_err_over_max", parity_record)
+    rsq_ref = r.reshape(c.batch, -1).square().sum(1)
+    rsq_err = float((part.double().sum(1).cpu() / rsq_ref - 1).abs().max())
+    parity_record("pass1_rsq_max_rel_err", rsq_err, BOUND)
+    assert rsq_err <= BOUND, rsq_err
+    # composed: x0, A x0, the residual in torch, A^T
+    x0d = torch.empty_like(xd)
+    _hip.check(run.lib.sp_predict_x0(xd.data_ptr(), ed.data_ptr(), xd.numel(), a, k, x0d.data_ptr(),
+                                     _stream()), "sp_predict_x0")
+    res = (gs * (yd.repeat_interleave(c.ydiv, dim=0) - run.apply(x0d))).contiguous()
+    comp = run.adjoint(res)
+    err = float((v - comp).abs().max() / comp.abs().max())
+    parity_record("pass1_v_fused_vs_composed_over_max", err, BOUND)
+    assert err <= BOUND, err
+    # bitwise: the same call twice, the last sample alone, y repeated at y_div 1, the _sched_ws form
+    v2, part2 = run.residual(xd, ed, yd, c.ydiv, coefs)
+    assert torch.equal(v2, v) and torch.equal(part2, part)
+    v1, part1 = run.residual(xd[-1:], ed[-1:], yd[(c.batch - 1) // c.ydiv:], 1, coefs)
+    assert torch.equal(v1, v[-1:]) and torch.equal(part1, part[-1:])
+    vr, partr = run.residual(xd, ed, yd.repeat_interleave(c.ydiv, dim=0).contiguous(), 1, coefs)
+    assert torch.equal(vr, v) and torch.equal(partr, part)
+    vs, parts = run.residual(xd, ed, yd, c.ydiv, coefs, sched=_sched_of(coefs, cuda))
+    assert torch.equal(vs, v) and torch.equal(parts, part)
+    # pass 2 is the identity-kind update over v
+    out = ec.Guarded((c.batch, c.n), 64, cuda)
+    wd, = _flat(cuda, c.xi)
+    _hip.check(run.lib.sp_dps_update(desc, xd.data_ptr(), ed.data_ptr(), yd.data_ptr(), v.data_ptr(),
+                                     wd.data_ptr(), part.data_ptr(), None, 7, 3, 2, c.batch, c.ydiv,
+                                     coefs, out.ptr(), _stream()), "sp_dps_update")
+    assert torch.isfinite(out.check()).all()
+
+
+@_params
+def test_pgdm_pass_1(cuda, parity_record, i, batch, ydiv):
+    """v = gs A^+ (y - A x0) against the reference and against sp_op_apply_ws / sp_op_pinv_ws."""
+    c = _case(i, batch, ydiv)
+    op, desc = c.dev(cuda)
+    run = Run(cuda, desc, c.n, c.m)
+    a, k, gs = 0.3, math.sqrt(1 - 0.09), -2.0
+    coefs = _hip.SpDpsCoefs(a, k, gs, 0.9, 0.2, 0.1, 0.05, 1e-9)
+    xd, ed, yd = _flat(cuda, c.x, c.eps, c.y)
+    q = run.prepare(yd, prox=False)
+    v = run.pgdm(xd, ed, q, c.ydiv, coefs)
+    x0 = (c.x.double() - k * c.eps.double()) / a
+    ref = gs * c.ref.pinv(c.rows.double() - c.ref.A(x0))
+    _close(v, ref, "pgdm_v_max_err_over_max", parity_record)
+    x0d = torch.empty_like(xd)
+    _hip.check(run.lib.sp_predict_x0(xd.data_ptr(), ed.data_ptr(), xd.numel(), a, k, x0d.data_ptr(),
+                                     _stream()), "sp_predict_x0")
+    res = (yd.repeat_interleave(c.ydiv, dim=0) - run.apply(x0d)).contiguous()
+    comp = gs * run.pinv(res, 0)
+    err = float((v - comp).abs().max()) / float(ref.abs().max())
+    parity_record("pgdm_v_fused_vs_composed_over_max", err, BOUND)
+    assert err <= BOUND, err
+    # bitwise: twice, a sample alone, y_div against repeated rows
+    assert torch.equal(run.pgdm(xd, ed, q, c.ydiv, coefs), v)
+    q1 = run.prepare(yd[(c.batch - 1) // c.ydiv:][:1].contiguous(), prox=False)
+    assert torch.equal(run.pgdm(xd[-1:], ed[-1:], q1, 1, coefs), v[-1:])
+    qr = run.prepare(yd.repeat_interleave(c.ydiv, dim=0).contiguous(), prox=False)
+    assert torch.equal(run.pgdm(xd, ed, qr, 1, coefs), v)
+
+
+def _f32(v):
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+@pytest.mark.parametrize("rho", pr.RHOS)
+@_params
+def test_prox_and_diffpir_step(cuda, parity_record, i, batch, ydiv, rho):
+    c = _case(i, batch, ydiv)
+    op, desc = c.dev(cuda)
+    run = Run(cuda, desc, c.n, c.m)
+    rho = _f32(rho)
+    vals = dict(a=_f32(0.8), k=_f32(0.6), a_prev=_f32(0.9), c_eps=_f32(0.35), c_xi=_f32(0.25))
+    coefs = _hip.SpProxCoefs(vals["a"], vals["k"], rho, vals["a_prev"], vals["c_eps"], vals["c_xi"])
+    M = c.ref.M
+    prox = lambda x0, y, r: so.spectral_prox(x0, y, M, c.s, r)  # noqa: E731  (x0's precision)
+    z64 = prox(c.x.double(), c.rows.double(), rho)
+    _, out64 = pr.step_from_prox(c.x.double(), c.eps.double(), c.xi.double(), c.rows.double(), prox,
+                                 rho, vals)
+    z32 = prox(c.x, c.rows, rho)
+    _, out32 = pr.step_from_prox(c.x, c.eps, c.xi, c.rows, prox, rho, vals)
+    xd, ed, xid, yd = _flat(cuda, c.x, c.eps, c.xi, c.y)
+    q = run.prepare(yd, prox=True)
+    z = run.prox(xd, q, c.ydiv, rho)
+    out = run.step(xd, ed, q, xid, c.ydiv, coefs)
+    p0 = torch.empty_like(xd)
+    _hip.check(run.lib.sp_predict_x0(xd.data_ptr(), ed.data_ptr(), xd.numel(), vals["a"], vals["k"],
+                                     p0.data_ptr(), _stream()), "sp_predict_x0")
+    comp = pr.diffpir_update(xd, run.prox(p0, q, c.ydiv, rho), xid, **vals)
+    for what, got, ref, ref32 in (("prox", z, z64, z32), ("step", out, out64, out32),
+                                  ("composed", comp, out64, out32)):
+        yard = _err(ref32, ref.reshape(ref32.shape))
+        _close(got, ref, f"{what}_max_err_over_max", parity_record, max(2e-5, 4 * yard), rho=rho,
+               fp32_fft=yard)
+    if rho != _f32(pr.RHOS[1]):
+        return
+    # bitwise: twice, x_out = x, a sample alone, y_div against repeated rows, xi = NULL is sp_randn
+    assert torch.equal(run.step(xd, ed, q, xid, c.ydiv, coefs), out)
+    assert torch.equal(run.step(xd, ed, q, xid, c.ydiv, coefs, alias=True), out)
+    q1 = run.prepare(yd[(c.batch - 1) // c.ydiv:][:1].contiguous(), prox=True)
+    assert torch.equal(run.step(xd[-1:], ed[-1:], q1, xid[-1:], 1, coefs), out[-1:])
+    assert torch.equal(run.prox(xd[-1:], q1, 1, rho), z[-1:])
+    qr = run.prepare(yd.repeat_interleave(c.ydiv, dim=0).contiguous(), prox=True)
+    assert torch.equal(run.step(xd, ed, qr, xid, 1, coefs), out)
+    drawn_xi = torch.empty_like(xd)
+    _hip.check(run.lib.sp_randn(drawn_xi.data_ptr(), c.batch, c.n, SEED, STEP, OFFSET, _stream()),
+               "sp_randn")
+    given = run.step(xd, ed, q, drawn_xi, c.ydiv, coefs)
+    drawn = run.step(xd, ed, q, None, c.ydiv, coefs)
+    assert torch.equal(drawn, given)
+    assert not torch.equal(run.step(xd, ed, q, None, c.ydiv, coefs, offset=OFFSET + 1), drawn)
+    # Operator.apply_prox on device tensors is sp_op_prox_ws
+    got = op.apply_prox(xd.reshape(c.batch, *c.shape), yd.repeat_interleave(c.ydiv, dim=0)
+                        .reshape(c.batch, *c.yshape), rho)
+    assert torch.equal(got.reshape(z.shape), z)
+
+
+# --- against the existing kinds -------------------------------------------------------------------
+@pytest.mark.parametrize("s", [2, 4, 8])
+def test_box_taps_are_the_sr_kind(cuda, parity_record, s):
+    shape = (2, 16, 24)
+    x = torch.randn(3, *shape, generator=torch.Generator().manual_seed(s)).to(cuda)
+    new = PeriodicSuperResolutionOperator(shape, torch.full((s,), 1.0 / s), factor=s).to(cuda)
+    old = SuperResolutionOperator(shape, s).to(cuda)
+    want = old.apply(x)
+    err = float((new.apply(x) - want).abs().max() / want.abs().max())
+    parity_record("apply_vs_sr_kind_over_max", err, BOUND)
+    assert err <= BOUND, err
+
+
+@pytest.mark.parametrize("i", [3, 5, 9], ids=[IDS[3], IDS[5], IDS[9]])
+def test_lattice_of_the_periodic_blur(cuda, parity_record, i):
+    """A against [::s, ::s] of SP_OP_PSF_PERIODIC's A with the taps embedded in a (K + s - 1)^2 odd
+    PSF: h'[u + R - pad] = h[u], R = (K + s) / 2 - 1."""
+    c = _case(i, 3, 3)
+    op, _ = c.dev(cuda)
+    h = torch.from_numpy(so.taps2d(c.taps)).float()
+    K, s = h.shape[0], c.s
+    R, pad = (K + s) // 2 - 1, (K - s) // 2
+    big = torch.zeros(2 * R + 1, 2 * R + 1)
+    big[R - pad:R - pad + K, R - pad:R - pad + K] = h
+    blur = PeriodicBlurOperator(c.shape, big).to(cuda)
+    x = c.x.to(cuda)
+    want = blur.apply(x)[..., ::s, ::s]
+    err = float((op.apply(x) - want).abs().max() / want.abs().max())
+    parity_record("apply_vs_periodic_blur_lattice_over_max", err, 2 * BOUND)
+    assert err <= 2 * BOUND, err  # two kernels, each within BOUND of the exact map
+
+
+# --- trajectories ---------------------------------------------------------------------------------
+SHAPE, B, N, SIGMA = (3, 32, 32), 2, 8, 0.05
+TAPS = {"bicubic4": lambda: bicubic_taps(4), "gauss16": lambda: gaussian_filter_taps(16, 3.0)}
+
+
+def _problem(name, cuda):
+    taps = TAPS[name]()
+    host = PeriodicSuperResolutionOperator(SHAPE, taps, factor=4)
+    kept = int(host.keep.sum())
+    assert kept < host.keep.numel() if name == "gauss16" else kept == host.keep.numel()
+    y = host.apply(si.fixture_x_true(B, SHAPE, 9))
+    y = y + SIGMA * torch.randn(tuple(y.shape), generator=torch.Generator().manual_seed(41))
+    prob = InverseProblem(PeriodicSuperResolutionOperator(SHAPE, taps, factor=4).to(cuda), y.to(cuda),
+                          GaussianNoise(SIGMA).to(cuda))
+    return host, so.Ref(taps, 32, 32, 4, host.keep), y, prob
+
+
+def _acp():
+    return torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1)
+
+
+@pytest.mark.parametrize("name", list(TAPS))
+def test_dps_matches_oracle(cuda, parity_record, name):
+    host, _, y, prob = _problem(name, cuda)
+    net = si.make_samplers_amd_net("conv", 3, 0.1, device=cuda)
+    init, steps = si.replay_noise(21, (B, *SHAPE), N)
+    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
+    out = DPSSampler(net)(prob, num_sampling_steps=N, gamma=1e-2, eta=1.0, noise_fn=fn)
+    core = si.EpsCore("conv", 3, 0.1)
+    ref = dps_loop.dps_reference(lambda x, t: core(x, t), _acp(),
+                                 si.leading_timesteps_ascending(N).tolist(), host.apply,
+                                 dps_loop.gaussian_log_prob(SIGMA), y, init, lambda i: steps[i],
+                                 gamma=1e-2, eta=1.0)
+    err = si.relative_error(out.cpu(), ref)
+    print("dps sr_periodic", name, err)
+    parity_record("dps_rel_l2", err, 1e-4)
+    assert err < 1e-4
+
+
+@pytest.mark.parametrize("name", list(TAPS))
+def test_pgdm_matches_oracle(cuda, parity_record, name, monkeypatch):
+    from samplers_amd.samplers import pgdm as pgdm_mod
+    from samplers_amd.samplers.dps import FusedDPSStep
+    from samplers_amd.samplers.pgdm import PGDMSampler
+
+    host, ref_ops, y, prob = _problem(name, cuda)
+    net = si.make_samplers_amd_net("conv", 3, 0.1, device=cuda)
+    init, steps = si.replay_noise(5, (B, *SHAPE), N)
+    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
+    made = []
+    real = pgdm_mod.make_dps_step
+    monkeypatch.setattr(pgdm_mod, "make_dps_step",
+                        lambda *a, **kw: made.append(real(*a, **kw)) or made[-1])
+    out = PGDMSampler(net)(prob, num_sampling_steps=N, guidance_weight=0.05, noise_fn=fn)
+    assert type(made[-1]) is FusedDPSStep and made[-1].grad_scale == -2.0 and made[-1].q is not None
+
+    def run(dt):
+        c = si.EpsCore("conv", 3, 0.1).to(dt)
+        return pgdm_reference(lambda x, t: c(x, t), _acp().to(dt),
+                              si.leading_timesteps_ascending(N).tolist(),
+                              lambda x: so.spectral_down(x, ref_ops.M, 4),
+                              lambda v: so.spectral_up(v, ref_ops.P, 4), y.to(dt), init.to(dt),
+                              lambda i: steps[i].to(dt), guidance_weight=0.05, eta=1.0)
+
+    ref = run(torch.float32)
+    cond = si.relative_error(run(torch.float64), ref)
+    bound = max(1e-4, 20 * cond)
+    err = si.relative_error(out.cpu(), ref)
+    print("pgdm sr_periodic", name, err, "bound", bound)
+    parity_record("pgdm_rel_l2", err, bound, fp32_to_fp64=cond)
+    assert err < bound
+
+
+@pytest.mark.parametrize("name", list(TAPS))
+def test_diffpir_matches_reference_loop(cuda, parity_record, name):
+    from samplers_amd.samplers import DiffPIRSampler
+
+    host, ref_ops, y, prob = _problem(name, cuda)
+    net = si.make_samplers_amd_net("conv", 3, 0.1, device=cuda)
+    init, steps = si.replay_noise(17, (B, *SHAPE), N)
+    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
+    out = DiffPIRSampler(net)(prob, num_sampling_steps=N, noise_fn=fn)
+    core = si.EpsCore("conv", 3, 0.1)
+    prox = lambda x0, yy, rho: so.spectral_prox(x0, yy, ref_ops.M, 4, float(rho))  # noqa: E731
+    ref = pr.diffpir_reference(lambda x, t: core(x, t), _acp(),
+                               si.leading_timesteps_ascending(N).tolist(), host.apply, prox, y, init,
+                               lambda i: steps[i], sigma=SIGMA)
+    err = si.relative_error(out.cpu(), ref)
+    print("diffpir sr_periodic", name, err)
+    parity_record("diffpir_rel_l2", err, 1e-4)
+    assert err < 1e-4
+
+
+@pytest.mark.parametrize("name", list(TAPS))
+def test_psld_matches_oracle(cuda, parity_record, name):
+    """Built as tests/test_radon_gpu.py::test_psld_matches_oracle; the kind is not SP_TRAIT_LINEAR,
+    so the step takes the generic route over the HIP A and A^T."""
+    from samplers_amd.samplers.psld import FusedPSLDStep, PSLDSampler
+
+    b, n_steps = 2, 6
+    taps = TAPS[name]()
+    host = PeriodicSuperResolutionOperator(SHAPE, taps, factor=4)
+    y = host.apply(si.fixture_x_true(b, SHAPE, 4))
+    y = y + 0.05 * torch.randn(tuple(y.shape), generator=torch.Generator().manual_seed(5))
+    prob = InverseProblem(PeriodicSuperResolutionOperator(SHAPE, taps, factor=4).to(cuda), y.to(cuda),
+                          GaussianNoise(0.05).to(cuda))
+    net = si.make_samplers_amd_latent_net("conv", 0.1, device=cuda)
+    lat = net.get_latent_shape(SHAPE)
+    step = FusedPSLDStep(net, prob, prob.observation.reshape(b, -1), 1, lat)
+    assert step.generic and step.m == 3 * 8 * 8 and step.n == 3 * 32 * 32
+    init, steps = si.replay_noise(13, (b, *lat), n_steps)
+    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
+    out = PSLDSampler(net)(prob, num_sampling_steps=n_steps, noise_fn=fn)
+    core, vae = si.EpsCore("conv", 4, 0.1), si.LatentCore()
+    ref = psld_reference(lambda x, t: core(x, t), _acp(),
+                         si.leading_timesteps_ascending(n_steps).tolist(),
+                         lambda x: host.apply(x.double()).float(),
+                         lambda v: host.apply_transpose(v.double()).float(),
+                         vae.decode, vae.encode, y, init, lambda i: steps[i])
+    err = si.relative_error(out.cpu(), ref)
+    print("psld sr_periodic", name, err)
+    parity_record("psld_rel_l2", err, 1e-4)
+    assert err < 1e-4
+
+
+# --- the bounds-checked library ---------------------------------------------------------------------
+def debug_sweep(cuda):
+    """Every entry point of the kind over the small cases; returns the outputs."""
+    outs = []
+    for i in range(BIG):
+        c = _case(i, 4, 2)
+        _, desc = c.dev(cuda)
+        run = Run(cuda, desc, c.n, c.m)
+        xd, ed, xid, cd, yd = _flat(cuda, c.x, c.eps, c.xi, c.cot, c.y)
+        outs += [run.apply(xd), run.adjoint(cd), run.pinv(cd, 0), run.pinv(xd, 1)]
+        coefs = _hip.SpDpsCoefs(0.3, 0.95, 400.0, 0.9, 0.2, 0.1, 0.05, 1e-9)
+        outs += list(run.residual(xd, ed, yd, 2, coefs))
+        outs += list(run.residual(xd, ed, yd, 2, coefs, sched=_sched_of(coefs, cuda)))
+        outs.append(run.pgdm(xd, ed, run.prepare(yd, prox=False), 2, coefs))
+        q = run.prepare(yd, prox=True)
+        pc = _hip.SpProxCoefs(0.8, 0.6, 0.37, 0.9, 0.35, 0.25)
+        outs += [run.prox(xd, q, 2, 0.37), run.step(xd, ed, q, xid, 2, pc), run.step(xd, ed, q, None, 2, pc)]
+    return outs
+
+
+DEBUG_CHILD = r"""
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[1] + "/tests")
+from samplers_amd import _hip
+import test_sr_periodic_gpu as T
+lib = _hip.load_library()
+assert lib.sp_debug_build() == 1, "not the debug library"
+_hip.debug_violations()  # clear
+outs = T.debug_sweep(torch.device("cuda:0"))
+nv, site = _hip.debug_violations()
+print("violations", nv, site, flush=True)
+assert nv == 0, (nv, site)
+assert all(bool(torch.isfinite(t).all()) for t in outs)
+print("debug build: clean", flush=True)
+"""
+
+
+def test_debug_build_has_no_violations(cuda):
+    """The kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh child
+    process (a process holds one library): every entry point over the ten small cases."""
+    if not _hip.DEBUG_LIB_PATH.exists():
+        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
+    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
+    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
+                         capture_output=True, text=True, timeout=240)
+    print(out.stdout[-4000:], out.stderr[-4000:])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "debug build: clean" in out.stdout
