@@ -25,7 +25,9 @@
  *     REQUIRES 16-byte aligned row buffers, y included where m == n (rows are n floats apart,
  *     so the base pointer decides): sp_dps_residual / sp_dps_update and their _sched forms, sp_residual_grad (m),
  *     sp_randn, sp_op_apply / sp_op_adjoint, sp_op_prox_ws, sp_diffpir_step_ws, sp_psld_pixel, sp_psld_cotangent,
- *     sp_pixel_opt_step, sp_ddim_eps_step, sp_stochastic_resample.  Packed INPAINT observation
+ *     sp_pixel_opt_step, sp_ddim_eps_step, sp_stochastic_resample, sp_op_prox_cg_ws and
+ *     sp_diffpir_step_cg_ws (x-space rows by n; y rows by m % 4 == 0, INPAINT's packed rows
+ *     included; work 16-byte aligned).  Elsewhere packed INPAINT observation
  *     rows (m elements) and partial-sum buffers are read by scalar loads and need only 4-byte
  *     alignment.  With n % 4 != 0 all access is scalar and 4-byte alignment suffices.
  *     PHASE: the kind's own launches read x, eps, y, g and write y, v, dx by scalar access (any
@@ -491,6 +493,66 @@ int sp_diffpir_step_ws(const sp_op* op, const float* x, const float* eps, const 
                        const float* q, const float* xi, uint64_t seed, int64_t step,
                        int64_t sample_offset, int64_t batch, int64_t y_div,
                        const sp_prox_coefs* coefs, float* x_out, float* work, sp_stream_t stream);
+
+/* ---- the proximal data step by conjugate gradients (csrc/sp_cg.hip; semantics in DESIGN.md §3
+ * and tests/prox_cg_ref.py) -----------------------------------------------------------------
+ * The same map z = (A^T A + rho I)^-1 (A^T y + rho x0) for EVERY linear kind, the ones without a
+ * closed form included, by regularised CGLS in d = z - x0, per sample:
+ *   s = y - A x0;  d = 0;  g = A^T s;  p = g;  gamma = |g|^2;  gamma0 = gamma;  iters = 0
+ *   max_iter times:
+ *     q = A p;  delta = |q|^2 + rho |p|^2
+ *     live = gamma > tol^2 gamma0  and  delta > 0  and  gamma, delta finite
+ *     live:  alpha = gamma / delta;  d += alpha p;  s -= alpha q;  g = A^T s - rho d;
+ *            gamma' = |g|^2;  p = g + (gamma' / gamma) p;  gamma = gamma';  iters += 1
+ *     else:  nothing of the sample changes (a select, never a product by 0), so the sample takes
+ *            the same decision at every later iteration: stopping is sticky
+ *   z = x0 + d
+ * The stop is part of the map, not an optimisation: without it gamma reaches rounding level, beta
+ * becomes noise and the fp32 recurrence leaves every bound.  y = A x0 gives
+ * gamma0 = 0, iters = 0 and z = x0 bit for bit.  A and A^T are the kind's own maps (sp_op_apply /
+ * sp_op_adjoint, or sp_op_apply_ws / sp_op_vjp_ws for the kinds whose maps need a workspace).
+ * Kinds: IDENTITY, INPAINT, MASK, BLUR, SR, PSF, RADON, PSF_FFT, PSF_PERIODIC, SR_PERIODIC; PHASE
+ * (nonlinear): SP_EUNSUPPORTED, after the argument checks.
+ * A call is one launch sequence of fixed length, max_iter x (A, A^T and four vector launches; the
+ * last iteration three), whatever the samples do: alpha, beta, gamma, delta and iters stay on the
+ * device, nothing synchronises with the host, there are no atomics and no grid-wide barriers.
+ * Every squared norm is sp_vec_partials(n) (x-space) or sp_vec_partials(m) (y-space) partials per
+ * sample summed in a fixed order and every sample is computed alone, so the bits of a sample do
+ * not depend on the batch, y_div, the shard or the other samples' stops.
+ *
+ * sp_prox_cg_workspace: floats of `work` for `batch` samples, step_form 0 (sp_op_prox_cg_ws) or 1
+ * (sp_diffpir_step_cg_ws).  With r4(v) = v rounded up to a multiple of 4,
+ *   (3 + step_form) * r4(batch * n)                       d, p, A^T s (g in place) [, x0]
+ *   + 2 * r4(batch * m)                                   s, q
+ *   + r4(batch * (3 * sp_vec_partials(n) + sp_vec_partials(m)))   gamma, gamma0, |p|^2; |q|^2
+ *   + 4 * batch                                           gamma, alpha, live, iters per sample
+ *   + sp_op_workspace(op, batch)                          the maps' own, last
+ * SP_EINVAL for a rejected descriptor, batch <= 0 or > 65535, step_form not 0 / 1;
+ * SP_EUNSUPPORTED for PHASE.  The library allocates nothing and writes nothing past that size.
+ *
+ * sp_op_prox_cg_ws: z_out = the map at x0 (batch rows of n), sample b against observation row
+ * b / y_div of y.  iters_out (batch int32, device) receives the live iterations of each sample;
+ * it may be NULL.  z_out may alias x0; work aliases nothing.  SP_EINVAL: rho <= 0 or non-finite,
+ * max_iter < 1, tol < 0 or non-finite, a null x0 / y / z_out / work, batch <= 0 or > 65535,
+ * y_div <= 0, a rejected descriptor.  Rows are 16-byte aligned where n (m) is a multiple of 4, as
+ * for every entry.
+ *
+ * sp_diffpir_step_cg_ws: the whole guided DiffPIR step of sp_diffpir_step_ws with this data step:
+ *   x0 = (x - k eps) / a,  z as above,  eps_hat = (x - a z) / k,
+ *   x' = a_prev z + (c_eps eps_hat + c_xi xi)
+ * with the reciprocals 1 / a and 1 / k taken once, xi injected or NULL for the Philox normals of
+ * sp_dps_update / sp_diffpir_step_ws, (seed, step, sample_offset + b, flat element index): the
+ * bits of sp_randn.  x_out may alias x.  SP_EINVAL as above, and for a null eps / coefs or
+ * k == 0. */
+int64_t sp_prox_cg_workspace(const sp_op* op, int64_t batch, int32_t step_form);
+int sp_op_prox_cg_ws(const sp_op* op, const float* x0, const float* y, int64_t batch, int64_t y_div,
+                     float rho, int32_t max_iter, float tol, float* z_out, int32_t* iters_out,
+                     float* work, sp_stream_t stream);
+int sp_diffpir_step_cg_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                          const float* xi, uint64_t seed, int64_t step, int64_t sample_offset,
+                          int64_t batch, int64_t y_div, const sp_prox_coefs* coefs,
+                          int32_t max_iter, float tol, float* x_out, int32_t* iters_out,
+                          float* work, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
  *   r = y[b/y_div] - z[b];  g[b] = grad_scale * r;  rsq_partial[b][p] += r^2 partials.

@@ -133,6 +133,12 @@ SIGNATURES = {
     "sp_op_prox_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _I64, _I64, _F, _P, _P, _P]),
     "sp_diffpir_step_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _P, _P, _U64, _I64, _I64, _I64, _I64,
                                           ctypes.POINTER(SpProxCoefs), _P, _P, _P]),
+    "sp_prox_cg_workspace": (_I64, [_OPP, _I64, ctypes.c_int32]),
+    "sp_op_prox_cg_ws": (ctypes.c_int, [_OPP, _P, _P, _I64, _I64, _F, ctypes.c_int32, _F, _P, _P,
+                                        _P, _P]),
+    "sp_diffpir_step_cg_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _P, _U64, _I64, _I64, _I64, _I64,
+                                             ctypes.POINTER(SpProxCoefs), ctypes.c_int32, _F, _P,
+                                             _P, _P, _P]),
     "sp_residual_grad": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "sp_psld_pixel": (ctypes.c_int, [_OPP, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "sp_sum_partials": (ctypes.c_int, [_P, _I64, _P, _P]),

@@ -621,7 +621,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 110; }
+int sp_version(void) { return 111; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 

@@ -55,7 +55,9 @@ typedef int pgdm_residual_fn(const sp_op* op, const float* x, const float* eps, 
 typedef int prox_fn(const sp_op* op, const prox_args& p, hipStream_t s);
 
 // One row per sp_op kind.  A null member is the library's answer for a kind without that pass:
-// 0 floats of workspace, or SP_EUNSUPPORTED (apply_ws: sp_op_apply).
+// 0 floats of workspace, or SP_EUNSUPPORTED (apply_ws: sp_op_apply).  The conjugate-gradient
+// proximal step (sp_cg.hip) has no column: it calls apply / adjoint, or apply_ws / vjp_ws with
+// op_workspace, of whichever linear kind it is given.
 struct op_kind {
     valid_fn* valid;        // the kind's geometry rules
     partials_fn* partials;  // r^2 partials per sample

@@ -68,6 +68,21 @@ class Operator(torch.nn.Module, ABC):
         raise NotImplementedError(f"{type(self).__name__} has no closed-form proximal map "
                                   "(apply_prox)")
 
+    def apply_prox_cg(self, x0: Tensor, y: Tensor, rho: float, iterations: int = 32,
+                      tol: float = 1e-6, return_iterations: bool = False):
+        """The same proximal map for every linear operator, by at most ``iterations`` steps of
+        regularised CGLS on ``(AᵀA + ρI) z = Aᵀy + ρ x0`` with a per-sample stop at
+        ``‖g‖² ≤ tol²·‖g₀‖²`` ("Proximal map by conjugate gradients"; the stop is
+        part of the map).  On host tensors the recurrence runs in plain torch in the tensor's
+        dtype through ``apply`` / ``apply_transpose``; on device tensors it is one call of
+        ``sp_op_prox_cg_ws`` (the operator needs a HIP descriptor).  With ``return_iterations``
+        the result is ``(z, iters)``, ``iters`` an int32 tensor of the batch shape: the live
+        iterations of each sample."""
+        rho, iterations, tol = check_cg(rho, iterations, tol)
+        run = _hip_prox_cg if x0.is_cuda else _host_prox_cg
+        z, iters = run(self, x0, y, rho, iterations, tol)
+        return (z, iters) if return_iterations else z
+
     def forward(self, x: Tensor) -> Tensor:
         return self.apply(x)
 
@@ -83,6 +98,11 @@ class NonlinearOperator(Operator):
 
     @abstractmethod
     def apply(self, x: Tensor) -> Tensor: ...
+
+    def apply_prox_cg(self, x0: Tensor, y: Tensor, rho: float, iterations: int = 32,
+                      tol: float = 1e-6, return_iterations: bool = False):
+        raise NotImplementedError(f"{type(self).__name__} is nonlinear: the conjugate-gradient "
+                                  "proximal map (apply_prox_cg) needs a linear operator")
 
 
 def _flatten_batch(t: Tensor, sample_shape: Shape) -> tuple[Tensor, tuple[int, ...]]:
@@ -218,6 +238,87 @@ def _hip_prox(op: Operator, x0: Tensor, y: Tensor, rho: float) -> Tensor:
         _hip.check(lib.sp_op_prox_ws(desc, _hip.ptr(flat), _hip.ptr(rows), _hip.ptr(q), n, 1, rho,
                                      _hip.ptr(out), _hip.ptr(work), stream), "sp_op_prox_ws")
     return out.reshape(*batch, *op.x_shape)
+
+
+def check_cg(rho: float, iterations: int, tol: float) -> tuple[float, int, float]:
+    rho, tol = check_rho(rho), float(tol)
+    if int(iterations) != iterations or int(iterations) < 1:
+        raise ValueError(f"iterations must be a positive integer, got {iterations!r}")
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError(f"tol must be non-negative and finite, got {tol}")
+    return rho, int(iterations), tol
+
+
+def _host_prox_cg(op: Operator, x0: Tensor, y: Tensor, rho: float, iterations: int,
+                  tol: float) -> tuple[Tensor, Tensor]:
+    """The recurrence of ``apply_prox_cg`` on host tensors, every sample with scalars of its own
+    (tensors of the flat batch): a sample that is not live keeps every vector through
+    ``torch.where``, never through a product by 0."""
+    flat, batch = _flatten_batch(x0.detach(), op.x_shape)
+    rows, y_batch = _flatten_batch(y.detach(), op.y_shape)
+    if y_batch != batch:
+        raise ValueError(f"x0 and y must share their batch dimensions, got {batch} and {y_batch}")
+    nb = flat.shape[0]
+    sq = lambda t: (t.reshape(nb, -1) ** 2).sum(1)  # noqa: E731
+    per = lambda v, t: v.reshape(nb, *([1] * (t.ndim - 1)))  # noqa: E731
+    s = rows - op.apply(flat)
+    d = torch.zeros_like(flat)
+    g = op.apply_transpose(s)
+    p = g.clone()
+    gamma = sq(g)
+    gamma0 = gamma.clone()
+    iters = torch.zeros(nb, dtype=torch.int32, device=flat.device)
+    for _ in range(iterations):
+        q = op.apply(p)
+        delta = sq(q) + rho * sq(p)
+        live = ((gamma > (tol * tol) * gamma0) & (delta > 0) & torch.isfinite(gamma)
+                & torch.isfinite(delta))
+        if not bool(live.any()):
+            break  # every sample has stopped, and stopping is sticky
+        alpha = gamma / delta
+        d = torch.where(per(live, d), d + per(alpha, d) * p, d)
+        s = torch.where(per(live, s), s - per(alpha, s) * q, s)
+        g = torch.where(per(live, g), op.apply_transpose(s) - rho * d, g)
+        gamma_new = sq(g)
+        p = torch.where(per(live, p), g + per(gamma_new / gamma, p) * p, p)
+        gamma = torch.where(live, gamma_new, gamma)
+        iters = iters + live.to(torch.int32)
+    z = torch.where(per(iters > 0, flat), flat + d, flat)
+    return z.reshape(*batch, *op.x_shape), iters.reshape(batch)
+
+
+def _hip_prox_cg(op: Operator, x0: Tensor, y: Tensor, rho: float, iterations: int,
+                 tol: float) -> tuple[Tensor, Tensor]:
+    """``sp_op_prox_cg_ws`` on device tensors: ``x0`` of shape ``(*batch, *x_shape)``, one row of
+    ``y`` per sample."""
+    name = type(op).__name__
+    _hip.require_cuda(y, name)
+    desc = op.hip_descriptor()
+    if desc is None:
+        raise NotImplementedError(f"{name} has no native (HIP) kernels: apply_prox_cg runs on "
+                                  "host tensors only")
+    if x0.dtype != torch.float32 or y.dtype != torch.float32:
+        raise _hip.HipLibraryError(f"{name}: HIP operators compute in fp32")
+    lib = _hip.load_library()
+    flat, batch = _flatten_batch(x0.detach(), op.x_shape)
+    rows, y_batch = _flatten_batch(y.detach(), op.y_shape)
+    if y_batch != batch:
+        raise ValueError(f"x0 and y must share their batch dimensions, got {batch} and {y_batch}")
+    out = torch.empty_like(flat)
+    n = flat.shape[0]
+    iters = torch.zeros(n, device=flat.device, dtype=torch.int32)
+    if n > 0:
+        floats = int(lib.sp_prox_cg_workspace(desc, n, 0))
+        if floats == -3:  # SP_EUNSUPPORTED: a nonlinear kind
+            raise NotImplementedError(f"{name}: the library has no linear maps for its kind "
+                                      "(apply_prox_cg)")
+        if floats < 0:
+            raise _hip.HipLibraryError(f"sp_prox_cg_workspace rejected the descriptor ({floats})")
+        work = torch.empty(floats, device=flat.device, dtype=torch.float32)
+        _hip.check(lib.sp_op_prox_cg_ws(desc, _hip.ptr(flat), _hip.ptr(rows), n, 1, rho, iterations,
+                                        tol, _hip.ptr(out), _hip.ptr(iters), _hip.ptr(work),
+                                        _hip.stream_of(x0)), "sp_op_prox_cg_ws")
+    return out.reshape(*batch, *op.x_shape), iters.reshape(batch)
 
 
 MIN_SIZE, MAX_SIZE = 8, 1024

@@ -8,14 +8,18 @@ and in fp64 by ``tests/prox_ref.py``.  The loop is ``PGDMSampler``'s (``i = len(
     eps = unet(x, t)                                      the prior, under no_grad: no VJP
     x  <- sp_diffpir_step_ws(x, eps, y | q, noise)        HIP: x0, the proximal data step, the update
 
-with ``x0 = (x − k·eps)/a``, ``z = argmin_u ‖y − A u‖² + ρ_t ‖u − x0‖²`` in closed form,
+with ``x0 = (x − k·eps)/a``, ``z = argmin_u ‖y − A u‖² + ρ_t ‖u − x0‖²``,
 ``eps_hat = (x − a·z)/k`` and ``x' = a_prev·z + k_prev·(sqrt(1−ζ)·eps_hat + sqrt(ζ)·ξ)``, where
 ``ρ_t = λ · max(σ_n, σ_min)² · ᾱ_t / (1 − ᾱ_t)``.  The network is called once per step and never
 differentiated, which is where the step's time goes in DPS and PGDM.
 
-Only the operators whose proximal map has a closed form run (``Operator.apply_prox``: identity,
-inpainting / mask, ×s super-resolution, periodic blur, periodic blur-and-decimate
-super-resolution); the others raise ``NotImplementedError``.
+``prox="closed_form"`` (the default) runs only the operators whose proximal map has a closed form
+(``Operator.apply_prox``: identity, inpainting / mask, ×s super-resolution, periodic blur, periodic
+blur-and-decimate super-resolution); the others raise ``NotImplementedError``.  ``prox="cg"``
+computes ``z`` by ``cg_iterations`` steps of conjugate gradients with a per-sample stop at
+``cg_tol`` (``sp_diffpir_step_cg_ws``, ``Operator.apply_prox_cg``) for every linear operator with
+a HIP descriptor: the Gaussian, PSF and FFT blurs and the Radon transform too.  ``prox="auto"``
+takes the closed form where there is one and conjugate gradients elsewhere.
 The noise model must be ``GaussianNoise``: σ_n enters ρ_t.  The step runs eagerly (no graph
 replay form).  Noise sources (``rng`` / ``seed`` / ``noise_fn``) are ``DPSSampler``'s.
 """
@@ -55,16 +59,34 @@ def prox_descriptor(operator) -> "_hip.SpOp":
     return desc
 
 
+PROX_MODES = ("closed_form", "cg", "auto")
+
+
+def cg_descriptor(operator) -> "_hip.SpOp":
+    """The operator's HIP descriptor if ``sp_diffpir_step_cg_ws`` serves its kind (every linear
+    kind; ``sp_prox_cg_workspace`` is the probe), else ``NotImplementedError`` naming it."""
+    desc = getattr(operator, "hip_descriptor", lambda: None)()
+    if desc is None or int(_hip.load_library().sp_prox_cg_workspace(desc, 1, 1)) < 0:
+        raise NotImplementedError(
+            f"{type(operator).__name__} has no linear HIP maps for the conjugate-gradient "
+            "proximal step (prox='cg'): DiffPIR needs a linear operator with a HIP descriptor")
+    return desc
+
+
 class FusedDiffPIRStep:
     """One DiffPIR iteration over a flat batch: the prior's forward under ``no_grad`` and
     ``sp_diffpir_step_ws``.  Owns what is fixed across the steps: ``q`` (the prepared observation
     of the kinds that transform it, once per call), the workspace of a chunk and the micro-batch
-    chunks.  ``observation_rows`` as ``FusedDPSStep``."""
+    chunks.  ``observation_rows`` as ``FusedDPSStep``.  With ``prox="cg"`` (or ``"auto"`` on a kind
+    without a closed form) the data step is ``sp_diffpir_step_cg_ws``; ``iterations`` then holds the
+    live iterations of every step so far, an int32 device tensor ``(steps, batch)`` that the loop
+    appends to and never reads."""
 
     def __init__(self, network: EpsilonNetwork, inverse_problem: InverseProblem,
                  observation_rows: Tensor, y_div: int, *, guidance_weight: float = 7.0,
                  zeta: float = 0.3, min_noise_std: float = 1e-3, micro_batch: int | None = None,
-                 timer: KernelTimer | None = None) -> None:
+                 timer: KernelTimer | None = None, prox: str = "closed_form",
+                 cg_iterations: int = 16, cg_tol: float = 1e-4) -> None:
         op, noise = inverse_problem.operator, inverse_problem.noise
         if not isinstance(noise, GaussianNoise):
             raise ValueError(f"DiffPIR needs GaussianNoise (its sigma sets rho), got "
@@ -76,7 +98,19 @@ class FusedDiffPIRStep:
             raise ValueError(f"zeta must be in [0, 1], got {zeta}")
         if not self.guidance_weight > 0.0:
             raise ValueError(f"guidance_weight must be positive, got {guidance_weight}")
-        self.desc = prox_descriptor(op)
+        if prox not in PROX_MODES:
+            raise ValueError(f"prox must be one of {PROX_MODES}, got {prox!r}")
+        if int(cg_iterations) != cg_iterations or int(cg_iterations) < 1:
+            raise ValueError(f"cg_iterations must be a positive integer, got {cg_iterations!r}")
+        if not (float(cg_tol) >= 0.0 and float(cg_tol) < float("inf")):
+            raise ValueError(f"cg_tol must be non-negative and finite, got {cg_tol}")
+        self.cg_iterations, self.cg_tol = int(cg_iterations), float(cg_tol)
+        self.cg = prox == "cg"
+        if prox == "auto":  # the closed form where sp_prox_workspace has one
+            desc = getattr(op, "hip_descriptor", lambda: None)()
+            self.cg = desc is None or int(_hip.load_library().sp_prox_workspace(desc, 1)) < 0
+        self.desc = cg_descriptor(op) if self.cg else prox_descriptor(op)
+        self.iterations: Tensor | None = None
         _hip.require_cuda(observation_rows, "DiffPIRSampler")
         if observation_rows.dtype != torch.float32:
             raise TypeError("the HIP path computes in fp32; cast the observation to float32")
@@ -87,10 +121,12 @@ class FusedDiffPIRStep:
         self.micro_batch, self.timer = micro_batch, timer
         self._work: Tensor | None = None
         rows = self.y.shape[0]
+        self.q = None
+        if self.cg:  # nothing to prepare: the maps read y itself
+            return
         qsize = int(lib.sp_prox_prepare_size(self.desc, rows))
         if qsize < 0:
             raise _hip.HipLibraryError(f"sp_prox_prepare_size rejected the descriptor ({qsize})")
-        self.q = None
         if qsize:
             self.q = torch.empty((rows, qsize // rows), device=self.y.device, dtype=torch.float32)
             _hip.check(lib.sp_prox_prepare(self.desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
@@ -107,9 +143,10 @@ class FusedDiffPIRStep:
     def workspace(self, batch: int, like: Tensor) -> Tensor | None:
         """The step's work buffer for ``batch`` samples (``sp_prox_workspace`` floats), kept
         between steps; None where the kind needs none."""
-        if self.q is None:
+        if self.q is None and not self.cg:
             return None
-        floats = int(self.lib.sp_prox_workspace(self.desc, batch))
+        floats = int(self.lib.sp_prox_cg_workspace(self.desc, batch, 1) if self.cg
+                     else self.lib.sp_prox_workspace(self.desc, batch))
         if floats < 0:
             raise _hip.HipLibraryError(f"sp_prox_workspace rejected the descriptor ({floats})")
         if self._work is None or self._work.numel() < floats or self._work.device != like.device:
@@ -121,6 +158,7 @@ class FusedDiffPIRStep:
         """Advance ``x`` (flat ``(B, *x_shape)``, contiguous fp32) one step, in place."""
         coefs = self.coefficients(t, t_prev)
         stream = _hip.stream_of(x)
+        iters = torch.zeros(x.shape[0], device=x.device, dtype=torch.int32) if self.cg else None
         for b0, b1 in self._chunks(x.shape[0]):
             xc, bc, row = x[b0:b1], b1 - b0, b0 // self.y_div
             with torch.no_grad():
@@ -130,19 +168,30 @@ class FusedDiffPIRStep:
             span = self.timer.span("diffpir_step", bc) if self.timer else None
             if span:
                 span.__enter__()
-            _hip.check(self.lib.sp_diffpir_step_ws(
-                self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
-                _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed, step,
-                sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
-                _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_ws")
+            if self.cg:
+                _hip.check(self.lib.sp_diffpir_step_cg_ws(
+                    self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]), _hip.ptr(xic),
+                    seed, step, sample_offset + b0, bc, self.y_div, coefs, self.cg_iterations,
+                    self.cg_tol, _hip.ptr(xc), _hip.ptr(iters[b0:b1]),
+                    _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_cg_ws")
+            else:
+                _hip.check(self.lib.sp_diffpir_step_ws(
+                    self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
+                    _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed, step,
+                    sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
+                    _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_ws")
             if span:
                 span.__exit__(None, None, None)
+        if iters is not None:  # appended on the device; nothing here waits for it
+            self.iterations = (iters[None] if self.iterations is None
+                               else torch.cat([self.iterations, iters[None]]))
         return x
 
 
 class DiffPIRSampler(PosteriorSampler, Generic[Condition_co]):
-    """DiffPIR (Zhu et al., 2023): one network call per step, the data step a closed-form
-    proximal map fused with the update into the operator's HIP launches."""
+    """DiffPIR (Zhu et al., 2023): one network call per step, the data step a proximal map (in
+    closed form, or by conjugate gradients for the linear operators without one) fused with the
+    update into HIP launches."""
 
     def __call__(
         self,
@@ -161,11 +210,17 @@ class DiffPIRSampler(PosteriorSampler, Generic[Condition_co]):
         sample_offset: int = 0,
         micro_batch: int | None = None,
         timer: KernelTimer | None = None,
+        prox: str = "closed_form",
+        cg_iterations: int = 16,
+        cg_tol: float = 1e-4,
         **kwargs,
     ) -> Tensor:
         """Run DiffPIR; returns ``(*batch_shape, R, *x_shape)`` (R squeezed when 1).
         ``guidance_weight`` is λ, ``zeta`` the share of fresh noise in a step, ``min_noise_std``
-        the floor of σ_n inside ρ_t; the keyword-only options are ``PGDMSampler``'s."""
+        the floor of σ_n inside ρ_t; the keyword-only options are ``PGDMSampler``'s, and
+        ``prox`` (``"closed_form"``, ``"cg"`` or ``"auto"``), ``cg_iterations`` and ``cg_tol``
+        choose the data step (module docstring).  The step object of the last call stays on the
+        sampler as ``last_step`` (its ``iterations``: the conjugate-gradient counts per step)."""
         if args or kwargs:
             print(f"Warning: Unused args={args}, kwargs={kwargs} in DiffPIRSampler")
         operator = inverse_problem.operator
@@ -183,7 +238,9 @@ class DiffPIRSampler(PosteriorSampler, Generic[Condition_co]):
             step = FusedDiffPIRStep(net, inverse_problem, y_rows, num_reconstructions,
                                     guidance_weight=guidance_weight, zeta=zeta,
                                     min_noise_std=min_noise_std, micro_batch=micro_batch,
-                                    timer=timer)
+                                    timer=timer, prox=prox, cg_iterations=cg_iterations,
+                                    cg_tol=cg_tol)
+            self.last_step = step
             if seed is None and noise_fn is None and rng == "philox":
                 seed = draw_seed()
             seed = int(seed or 0)
