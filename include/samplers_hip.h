@@ -1,6 +1,6 @@
 /*
  * samplers_hip.h — C ABI of libsamplers_hip.so, the MI355X (gfx950) hot path of
- * diffusion posterior sampling (DPS / PSLD / PGDM / ReSample / DiffPIR guidance steps).
+ * diffusion posterior sampling (DPS / PSLD / PGDM / ReSample / DiffPIR / DDRM guidance steps).
  *
  * The reference (thomashirtz/samplers) is pure Python over PyTorch; every entry
  * point below replaces a group of eager ATen calls that the reference issues
@@ -24,7 +24,7 @@
  *     point over rows of n (or m) elements chooses float4 access from n % 4 == 0 alone and then
  *     REQUIRES 16-byte aligned row buffers, y included where m == n (rows are n floats apart,
  *     so the base pointer decides): sp_dps_residual / sp_dps_update and their _sched forms, sp_residual_grad (m),
- *     sp_randn, sp_op_apply / sp_op_adjoint, sp_op_prox_ws, sp_diffpir_step_ws, sp_psld_pixel, sp_psld_cotangent,
+ *     sp_randn, sp_op_apply / sp_op_adjoint, sp_op_prox_ws, sp_diffpir_step_ws, sp_ddrm_step_ws, sp_psld_pixel, sp_psld_cotangent,
  *     sp_pixel_opt_step, sp_ddim_eps_step, sp_stochastic_resample, sp_op_prox_cg_ws and
  *     sp_diffpir_step_cg_ws (x-space rows by n; y rows by m % 4 == 0, INPAINT's packed rows
  *     included; work 16-byte aligned).  Elsewhere packed INPAINT observation
@@ -553,6 +553,60 @@ int sp_diffpir_step_cg_ws(const sp_op* op, const float* x, const float* eps, con
                           int64_t batch, int64_t y_div, const sp_prox_coefs* coefs,
                           int32_t max_iter, float tol, float* x_out, int32_t* iters_out,
                           float* work, sp_stream_t stream);
+
+/* ---- DDRM / spectral step (no reference counterpart: Kawar et al. 2022, eq. 7-8 in the VP
+ * variables; semantics in DESIGN.md §3 and tests/ddrm_ref.py) --------------------------------
+ * With A = U S V^T, x0 = (x - k eps) / a and ybar = S^+ U^T y, every spectral component of the
+ * next sample is set by the class of its singular value s (sig_prev = sqrt(1 - abar') / sqrt(abar'),
+ * c1 = sqrt(1 - eta^2)):
+ *   unobserved (s = 0 or outside the kept set)   f_th = 1, f_eps = c1 sig_prev, f_y = 0, f_xi = eta sig_prev
+ *   observed, small (sig_prev s < sig_y)         f_th = 1 - r, f_y = r = c1 sig_prev s / sig_y, f_xi = eta sig_prev
+ *   observed, big   (sig_prev s >= sig_y)        f_th = 1 - eta_b, f_y = eta_b,
+ *                                                f_xi = sqrt(max(sig_prev^2 - eta_b^2 sig_y^2 / s^2, 0))
+ *   x' = a_prev V [f_th V^T x0 + f_eps V^T eps + f_y ybar + f_xi V^T xi],  xi ~ N(0, I) in space.
+ * The class is the one fp32 expression (sig_prev * sig_prev) * s2 >= sig_y * sig_y with
+ * s2 = re * re + im * im of the multiplier M (PSF_PERIODIC) or the kind's constant (1; SR: 1 / factor^2),
+ * every operation rounded on its own: no division, no square root, no contraction.  The kinds:
+ *   IDENTITY, INPAINT, MASK (A A^T = I)  one launch; an observed element is f_th x0 + f_y y + f_xi xi,
+ *                                        an unobserved one x0 + c1 sig_prev eps + eta sig_prev xi;
+ *   SR x s (A A^T = I / s^2)             one launch, the projector form: with mean() the block mean
+ *                                        in the order of csrc/sp_sr.hip,
+ *        x' / a_prev = x0 + c1 sig_prev eps + eta sig_prev xi + (f_th - 1) mean(x0)
+ *                      - c1 sig_prev mean(eps) + (f_xi - eta sig_prev) mean(xi) + f_y y;
+ *   PSF_PERIODIC (V^T = FFT2)            three launches through work: row transforms of x0, eps and
+ *                                        xi (drawn while staging); per column tile the three column
+ *                                        transforms, F = f_th X0 + f_eps E + f_xi Xi + f_y q
+ *                                        (s = |M| where P != 0, unobserved elsewhere; q as
+ *                                        sp_pgdm_prepare writes it), one inverse column transform;
+ *                                        inverse rows, real part, times a_prev.
+ * Every other kind: SP_EUNSUPPORTED.  1 / a is taken once per thread.  Plain stores, no atomics;
+ * every sample is computed alone, so the bits do not depend on the batch, y_div or the shard. */
+typedef struct sp_ddrm_coefs {
+    float a;        /* sqrt(alpha_bar[t])                                      */
+    float k;        /* sqrt(1 - alpha_bar[t])                                  */
+    float a_prev;   /* sqrt(alpha_bar[t_prev])                                 */
+    float sig_prev; /* sqrt(1 - alpha_bar[t_prev]) / sqrt(alpha_bar[t_prev])   */
+    float sig_y;    /* observation noise std, >= 0                             */
+    float eta;      /* in [0, 1]                                               */
+    float eta_b;    /* in [0, 1]                                               */
+    float c1;       /* sqrt(1 - eta^2), computed in fp64 by the caller         */
+} sp_ddrm_coefs;    /* 32 bytes */
+/* Floats of `work` that sp_ddrm_step_ws needs for `batch` samples: 0 for the one-launch kinds,
+ * three intermediates (3 * sp_op_workspace) for PSF_PERIODIC.  This is the capability probe:
+ * SP_EUNSUPPORTED for a valid kind without a DDRM step (BLUR, PSF, PHASE, PSF_FFT, RADON,
+ * SR_PERIODIC), SP_EINVAL for a rejected descriptor or batch <= 0. */
+int64_t sp_ddrm_workspace(const sp_op* op, int64_t batch);
+/* The whole DDRM step after the network call.  q: PSF_PERIODIC reads what sp_pgdm_prepare wrote
+ * (P FFT2(y) / (H W), row b / y_div) and not y; the one-launch kinds read y and q may be NULL.
+ * xi: injected standard normals (batch * n) or NULL to draw the Philox normals of sp_randn,
+ * (seed, step, sample_offset + b, flat element index).  x_out may alias x; work aliases nothing.
+ * SP_EINVAL: a null x, eps, coefs or x_out; a null y (or q) or work where it is read; batch <= 0
+ * or > 65535; y_div <= 0; a == 0; eta or eta_b outside [0, 1]; a negative or non-finite sig_y or
+ * sig_prev. */
+int sp_ddrm_step_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                    const float* q, const float* xi, uint64_t seed, int64_t step,
+                    int64_t sample_offset, int64_t batch, int64_t y_div,
+                    const sp_ddrm_coefs* coefs, float* x_out, float* work, sp_stream_t stream);
 
 /* Likelihood gradient in y-space (noise.py:19-27 score, 77-79, 121-123):
  *   r = y[b/y_div] - z[b];  g[b] = grad_scale * r;  rsq_partial[b][p] += r^2 partials.

@@ -74,6 +74,12 @@ class SpProxCoefs(ctypes.Structure):
     _fields_ = [(f, ctypes.c_float) for f in ("a", "k", "rho", "a_prev", "c_eps", "c_xi")]
 
 
+class SpDdrmCoefs(ctypes.Structure):
+    """Scalars of one DDRM step (include/samplers_hip.h sp_ddrm_coefs), 32 bytes."""
+    _fields_ = [(f, ctypes.c_float) for f in ("a", "k", "a_prev", "sig_prev", "sig_y", "eta",
+                                              "eta_b", "c1")]
+
+
 class SpStepRec(ctypes.Structure):
     """One record of the device-resident step schedule (include/samplers_hip.h)."""
     _fields_ = [("c", SpDpsCoefs), ("step", ctypes.c_int64), ("t", ctypes.c_int64)]
@@ -139,6 +145,9 @@ SIGNATURES = {
     "sp_diffpir_step_cg_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _P, _U64, _I64, _I64, _I64, _I64,
                                              ctypes.POINTER(SpProxCoefs), ctypes.c_int32, _F, _P,
                                              _P, _P, _P]),
+    "sp_ddrm_workspace": (_I64, [_OPP, _I64]),
+    "sp_ddrm_step_ws": (ctypes.c_int, [_OPP, _P, _P, _P, _P, _P, _U64, _I64, _I64, _I64, _I64,
+                                       ctypes.POINTER(SpDdrmCoefs), _P, _P, _P]),
     "sp_residual_grad": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "sp_psld_pixel": (ctypes.c_int, [_OPP, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "sp_sum_partials": (ctypes.c_int, [_P, _I64, _P, _P]),

@@ -355,6 +355,88 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_prox(
 }
 
 // ---------------------------------------------------------------------------
+// K4: the DDRM step of IDENTITY / INPAINT / MASK (A A^T = I: every singular value is 1 and V is
+// the identity), one launch on K3's tiles and noise path.  With x0 = (x - k eps) / a:
+//   observed    x' = a_prev ((f_th x0 + f_y y) + f_xi xi)          f of ddrm_class_coefs(c, 1, true)
+//   unobserved  x' = a_prev ((x0 + (c1 sig_prev) eps) + (eta sig_prev) xi)
+// Both coefficient sets are the same for every element, so the host takes them once per launch
+// (ddrm_class_coefs is the one function on both sides).  Bytes per element: 12 + 4 per observed one
+// (x, eps read, x' written, y read), + 4 with xi injected; the keep words add 12 B per 64.
+// Roundings of the longest path (observed, small class): 1 / a, k eps, the difference, the product
+// with 1 / a (4, x0); f_th = 1 - r with r = ((c1 sig_prev) sqrt(1)) / sig_y (4) and its product
+// with x0 (1); two sums (2); the product with a_prev (1): 12.
+// ---------------------------------------------------------------------------
+template <int OPK, int V, bool XI_IN>
+__global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_ddrm(
+    sp_op op, const float* __restrict__ x, const float* __restrict__ eps,
+    const float* __restrict__ y, const float* __restrict__ xi, uint64_t seed, int64_t step,
+    int64_t sample_offset, int64_t y_div, sp_ddrm_coefs c, ddrm_f fo, ddrm_f fu,
+    float* __restrict__ out) {
+    const int64_t b = blockIdx.y;
+    const int64_t n = op.n;
+    const float* xb = x + b * n;
+    const float* eb = eps + b * n;
+    const float* yb = y + (b / y_div) * op.m;
+    float* ob = out + b * n;
+    const int64_t j0 = (int64_t)blockIdx.x * kIter * (kBlock * V) + threadIdx.x * V;
+    float xv[kIter][V], ev[kIter][V], yv[kIter][V];
+    uint32_t bits[kIter];
+    int64_t rank[kIter];
+#pragma unroll
+    for (int it = 0; it < kIter; ++it) {
+        const int64_t j = j0 + it * (kBlock * V);
+        if (j < n) {
+            SP_DCHECK(j + V <= n);
+            load_v<V, SP_UPD_NT>(xb + j, xv[it]);
+            load_v<V, SP_UPD_NT>(eb + j, ev[it]);
+            if constexpr (OPK == SP_OP_INPAINT) {
+                inpaint_lookup(op, j, bits[it], rank[it]);
+            } else {
+                load_v<V>(yb + j, yv[it]);
+                if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
+            }
+        }
+    }
+    if constexpr (OPK == SP_OP_INPAINT) {
+#pragma unroll
+        for (int it = 0; it < kIter; ++it) {
+            const int64_t j = j0 + it * (kBlock * V);
+            if (j < n) {
+                int64_t r = rank[it];
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    yv[it][e] = 0.f;
+                    if ((bits[it] >> e) & 1u) yv[it][e] = yb[r];
+                    r += (bits[it] >> e) & 1u;
+                }
+                SP_DCHECK(r <= op.m);  // packed observation index inside the row
+            }
+        }
+    }
+    const float inv_a = 1.f / c.a;
+#pragma unroll
+    for (int it = 0; it < kIter; ++it) {
+        const int64_t j = j0 + it * (kBlock * V);
+        if (j < n) {
+            float nz[V];
+            if constexpr (XI_IN) load_v<V>(xi + b * n + j, nz);
+            else philox_normals<V>(seed, step, sample_offset + b, j, nz);
+            float o[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+// every product and sum rounds on its own: the bits of the expression as written, in both noise forms
+#pragma clang fp contract(off)
+                const bool kept = OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+                const float x0 = (xv[it][e] - c.k * ev[it][e]) * inv_a;
+                o[e] = kept ? c.a_prev * ((fo.th * x0 + fo.y * yv[it][e]) + fo.xi * nz[e])
+                            : c.a_prev * ((x0 + fu.ep * ev[it][e]) + fu.xi * nz[e]);
+            }
+            store_v<V, true>(ob + j, o);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // elementwise helpers
 // ---------------------------------------------------------------------------
 template <int V>
@@ -545,12 +627,37 @@ static int elementwise_prox(const sp_op* op, const prox_args& p, hipStream_t s) 
     return check_launch(p.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws");
 }
 
+// the DDRM step of the elementwise kinds: one launch of K4
+static int elementwise_ddrm(const sp_op* op, const ddrm_args& p, hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>(tiles_elementwise(op->n)), static_cast<unsigned>(p.batch));
+    const bool v4 = op->n % 4 == 0;
+    const ddrm_f fo = ddrm_class_coefs(p.c, 1.f, true), fu = ddrm_class_coefs(p.c, 1.f, false);
+#define SP_K4(OPK, V, XIN)                                                                      \
+    launch(0, k_ddrm<OPK, V, XIN>, grid, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, p.step, \
+           p.sample_offset, p.y_div, p.c, fo, fu, p.out)
+#define SP_K4_FORM(OPK, V)         \
+    if (p.xi) SP_K4(OPK, V, true); \
+    else SP_K4(OPK, V, false)
+#define SP_K4_V(OPK) \
+    if (v4) { SP_K4_FORM(OPK, 4); } else { SP_K4_FORM(OPK, 1); }
+    switch (op->kind) {
+        case SP_OP_IDENTITY: SP_K4_V(SP_OP_IDENTITY) break;
+        case SP_OP_MASK: SP_K4_V(SP_OP_MASK) break;
+        default: SP_K4_V(SP_OP_INPAINT) break;
+    }
+#undef SP_K4_V
+#undef SP_K4_FORM
+#undef SP_K4
+    return check_launch("sp_ddrm_step_ws");
+}
+
 // The dispatch table: one row per kind, indexed by sp_op.kind (sp_ops.h)
 #define SP_ELEMENTWISE_ROW(VALID)                                                              \
     {VALID, elementwise_partials, nullptr, nullptr, elementwise_dps_residual,                  \
      elementwise_map<false>, elementwise_map<true>, nullptr, nullptr, elementwise_psld_pixel,  \
      elementwise_psld_cotangent, elementwise_pixel_opt, SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, \
-     nullptr, nullptr, nullptr, nullptr, nullptr, elementwise_prox, elementwise_prox}
+     nullptr, nullptr, nullptr, nullptr, nullptr, elementwise_prox, elementwise_prox, nullptr,     \
+     elementwise_ddrm}
 static const op_kind g_kinds[] = {
     /* SP_OP_IDENTITY */ SP_ELEMENTWISE_ROW(identity_valid),
     /* SP_OP_INPAINT */ SP_ELEMENTWISE_ROW(inpaint_valid),
@@ -563,7 +670,7 @@ static const op_kind g_kinds[] = {
     {sr_valid, sr_partials, nullptr, nullptr, sr_dps_residual, sr_apply, sr_adjoint, nullptr,
      nullptr, sr_psld_pixel, sr_psld_cotangent, sr_pixel_opt,
      SP_TRAIT_UPDATE_READS_V | SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, nullptr, nullptr, nullptr,
-     nullptr, nullptr, sr_prox, sr_prox},
+     nullptr, nullptr, sr_prox, sr_prox, nullptr, sr_ddrm},
     /* SP_OP_PSF: as BLUR, and two launches through the caller's work buffer (_ws forms) */
     {psf_valid, psf_partials, psf_workspace, nullptr, psf_dps_residual, psf_apply, psf_adjoint,
      nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
@@ -584,7 +691,8 @@ static const op_kind g_kinds[] = {
      psf_fft_dps_residual, nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr,
      nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
      psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual,
-     psf_fft_workspace, psf_periodic_prox_prepare, psf_periodic_prox, psf_periodic_prox},
+     psf_fft_workspace, psf_periodic_prox_prepare, psf_periodic_prox, psf_periodic_prox,
+     psf_periodic_ddrm_workspace, psf_periodic_ddrm},
     /* SP_OP_RADON: as PSF (project, then backproject through the caller's work buffer), with an
        observation space of its own geometry: m = channels * radius * factor */
     {radon_valid, radon_partials, radon_workspace, nullptr, radon_dps_residual, radon_apply,
@@ -621,7 +729,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 111; }
+int sp_version(void) { return 112; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -982,6 +1090,35 @@ int sp_diffpir_step_ws(const sp_op* op, const float* x, const float* eps, const 
                          work};
     if (!prox_buffers_ok(k, p)) return SP_EINVAL;
     return k->diffpir_step(op, p, static_cast<hipStream_t>(stream));
+}
+
+// ---- DDRM / spectral step ----
+int64_t sp_ddrm_workspace(const sp_op* op, int64_t batch) {
+    if (!valid_op(op) || batch <= 0) return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->ddrm_step) return SP_EUNSUPPORTED;
+    return k->ddrm_workspace ? k->ddrm_workspace(op, batch) : 0;
+}
+
+static bool ddrm_unit_ok(float v) { return v >= 0.f && v <= 1.f; }                  // NaN fails
+static bool ddrm_sigma_ok(float v) { return v >= 0.f && v <= 3.402823466e+38f; }  // NaN, inf fail
+
+int sp_ddrm_step_ws(const sp_op* op, const float* x, const float* eps, const float* y,
+                    const float* q, const float* xi, uint64_t seed, int64_t step,
+                    int64_t sample_offset, int64_t batch, int64_t y_div,
+                    const sp_ddrm_coefs* coefs, float* x_out, float* work, sp_stream_t stream) {
+    if (!valid_op(op) || !x || !eps || !coefs || !x_out || batch <= 0 || y_div <= 0 ||
+        batch > 65535 || coefs->a == 0.f || !ddrm_unit_ok(coefs->eta) ||
+        !ddrm_unit_ok(coefs->eta_b) || !ddrm_sigma_ok(coefs->sig_y) ||
+        !ddrm_sigma_ok(coefs->sig_prev))
+        return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    if (!k->ddrm_step) return SP_EUNSUPPORTED;
+    // the kind's own buffers: q and work for the kind with a workspace, y for the one-launch kinds
+    if (k->ddrm_workspace ? !q || !work : !y) return SP_EINVAL;
+    const ddrm_args p = {x, eps, y, q, xi, seed, step, sample_offset, batch, y_div, *coefs, x_out,
+                         work};
+    return k->ddrm_step(op, p, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -29,6 +29,36 @@ struct prox_args {
     float *out, *work;
 };
 
+// sp_ddrm_step_ws
+struct ddrm_args {
+    const float *x, *eps, *y, *q, *xi;  // y: the one-launch kinds; q: PSF_PERIODIC (sp_pgdm_prepare's)
+    uint64_t seed;
+    int64_t step, sample_offset, batch, y_div;
+    sp_ddrm_coefs c;
+    float *out, *work;
+};
+
+// The four coefficients of one spectral component of the DDRM step (samplers_hip.h): s2 is the
+// squared singular value, `observed` false outside the operator's kept set.  Every operation
+// rounds on its own; the class is decided without a division or a square root, so numpy float32
+// returns the same mask (tests/ddrm_ref.py).
+struct ddrm_f {
+    float th, ep, y, xi;
+};
+__host__ __device__ inline ddrm_f ddrm_class_coefs(const sp_ddrm_coefs& c, float s2, bool observed) {
+#pragma clang fp contract(off)
+    const float sp2 = c.sig_prev * c.sig_prev;
+    const float es = c.eta * c.sig_prev;
+    if (!observed || s2 == 0.f) return {1.f, c.c1 * c.sig_prev, 0.f, es};
+    if (sp2 * s2 >= c.sig_y * c.sig_y) {  // big: the measured value replaces (eta_b = 1) x0's
+        const float e = c.eta_b * c.sig_y;
+        const float v = sp2 - (e * e) / s2;
+        return {1.f - c.eta_b, 0.f, c.eta_b, __builtin_sqrtf(v > 0.f ? v : 0.f)};
+    }
+    const float r = ((c.c1 * c.sig_prev) * __builtin_sqrtf(s2)) / c.sig_y;  // < 1, sig_y > 0 here
+    return {1.f - r, 0.f, r, es};
+}
+
 typedef bool valid_fn(const sp_op* op);
 typedef int64_t partials_fn(const sp_op* op);
 typedef int64_t workspace_fn(const sp_op* op, int64_t batch);
@@ -53,6 +83,7 @@ typedef int pgdm_residual_fn(const sp_op* op, const float* x, const float* eps, 
                              int64_t batch, int64_t y_div, const sp_dps_coefs& c, float* v,
                              float* work, hipStream_t s);
 typedef int prox_fn(const sp_op* op, const prox_args& p, hipStream_t s);
+typedef int ddrm_fn(const sp_op* op, const ddrm_args& p, hipStream_t s);
 
 // One row per sp_op kind.  A null member is the library's answer for a kind without that pass:
 // 0 floats of workspace, or SP_EUNSUPPORTED (apply_ws: sp_op_apply).  The conjugate-gradient
@@ -81,6 +112,10 @@ struct op_kind {
     workspace_fn* prox_workspace;
     pgdm_prepare_fn* prox_prepare;
     prox_fn *prox, *diffpir_step;
+    // the kinds with a DDRM step (sp_ddrm_workspace answers for the others): the floats of work
+    // (null: none) and the step's launches
+    workspace_fn* ddrm_workspace;
+    ddrm_fn* ddrm_step;
 };
 
 const op_kind* kind_of(const sp_op* op);  // null for an unknown kind or a null op
@@ -110,6 +145,8 @@ psld_cotangent_fn elementwise_psld_cotangent, sr_psld_cotangent;
 pixel_opt_fn elementwise_pixel_opt, sr_pixel_opt;
 pgdm_prepare_fn psf_periodic_prox_prepare;
 prox_fn sr_prox, psf_periodic_prox;  // both forms: p.eps selects (elementwise kinds: sp_dps.hip)
+workspace_fn psf_periodic_ddrm_workspace;
+ddrm_fn sr_ddrm, psf_periodic_ddrm;  // the elementwise kinds' launch: sp_dps.hip
 // SP_OP_SR_PERIODIC (sp_psf_fft.hip, on the periodic kind's pipeline; psf_fft_workspace serves it)
 valid_fn sr_periodic_valid;
 partials_fn sr_periodic_partials;

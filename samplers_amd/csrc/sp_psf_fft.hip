@@ -52,7 +52,7 @@
 namespace sp {
 
 enum { PF_REFLECT = 0, PF_CIRCULAR = 1, PF_ZEROS = 2 };
-enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2, PF_OUT_PROX = 3, PF_OUT_PROX_ADD = 4 };
+enum { PF_OUT_A = 0, PF_OUT_AT = 1, PF_OUT_RESIDUAL = 2, PF_OUT_PROX = 3, PF_OUT_PROX_ADD = 4, PF_OUT_SCALE = 5 };
 enum { PF_COL_MAP = 0, PF_COL_PREPARE = 1, PF_COL_PGDM = 2, PF_COL_PROX = 3 };
 
 // what the PF_OUT_PROX epilogue of k_pf_rows_inv needs besides z (the other forms pass an empty
@@ -271,7 +271,8 @@ __global__ __launch_bounds__(kBlock) void k_pf_cols(pf_geom g, float2* __restric
 
 // launch 3.  OUT: PF_OUT_A columns 0 .. W-1 -> out; PF_OUT_AT columns 0 .. W+2R-1 folded onto W
 // -> out; PF_OUT_RESIDUAL the fused launch of DPS pass 1: g = gs (y - A x0) and the r^2 partial
-// of the tile, then the forward row transform of g back into the intermediate.
+// of the tile, then the forward row transform of g back into the intermediate; PF_OUT_SCALE
+// (the DDRM step's launch 3) gs times the real part -> out, on PF_OUT_PROX's float4 path.
 template <int OUT>
 __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __restrict__ ws,
                                                         float* __restrict__ out,
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
                 wp[kw * g.H + h] = f[t * NP + phase_slot(kw)];
             }
         }
-    } else if constexpr (OUT == PF_OUT_PROX || OUT == PF_OUT_PROX_ADD) {
+    } else if constexpr (OUT == PF_OUT_PROX || OUT == PF_OUT_PROX_ADD || OUT == PF_OUT_SCALE) {
         // z = the real part; four columns per thread (W % 4 == 0 for every transform length), so
         // x, xi and the output move as float4 and one Philox draw serves its four elements
         float* __restrict__ op_out = out + plane * g.H * g.W;
@@ -361,6 +362,10 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
             float o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = rl[phase_slot(j + e)].x;
+            if constexpr (OUT == PF_OUT_SCALE) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] *= gs;
+            }
             if constexpr (OUT == PF_OUT_PROX_ADD) {
                 float x0[4];
                 load_v<4>(xp + h * g.W + j, x0);
@@ -411,6 +416,172 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
                 op_out[h * g.W + j] = val;
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The DDRM step of SP_OP_PSF_PERIODIC (samplers_hip.h): the right singular basis is the 2-D DFT,
+// so x0, eps and the noise plane xi are transformed, combined per frequency and transformed back.
+// Three launches through three intermediates of the layout above, `stride` float2 apart:
+//   k_pf_rows_ddrm   row transforms of x0 = (x - k eps) / a, eps and xi (read, or drawn by Philox
+//                    at the flat element index while staging) -> ws[0], ws[1], ws[2];
+//   k_pf_cols_ddrm   per column tile the three forward column transforms, accumulated in registers
+//                    as F = (f_th X0 + f_eps E + f_xi Xi) / (H W) + f_y q, one inverse column
+//                    transform -> ws[0];
+//   k_pf_rows_inv<PF_OUT_SCALE>  inverse rows, a_prev times the real part -> x'.
+// A frequency is observed where P != 0, with s^2 = |M|^2; the class and the four coefficients are
+// ddrm_class_coefs' (sp_ops.h).  Bytes per element: 12 (x, eps read, x' written; + 4 with xi
+// injected) and the intermediates, (W / 2 + 1) / W * 8 B each: three written and read, one written
+// and read again, + 8 of q and 16 of M and P per stored frequency (the spectra are shared by the
+// batch).  Roundings of the longest path besides the transforms' own (4 log2 of each length,
+// three forward and one inverse pair): x0 (4), s^2 (3), f_th (5: sp2, the product, r's three,
+// 1 - r counted with them), its product with 1 / (H W) and with X0 (2), three sums (3), a_prev (1).
+// ---------------------------------------------------------------------------
+template <bool XI_IN>
+__global__ __launch_bounds__(kBlock) void k_pf_rows_ddrm(pf_geom g, const float* __restrict__ x,
+                                                         const float* __restrict__ eps,
+                                                         const float* __restrict__ xi, uint64_t seed,
+                                                         int64_t step, int64_t sample_offset, float a,
+                                                         float k, float2* __restrict__ ws,
+                                                         int64_t stride, int T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int N = g.Nw, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.H + T - 1) / T, per = g.C * tiles;
+    const int src = static_cast<int>(blockIdx.x) / per;  // 0: x0, 1: eps, 2: xi
+    const int rem = static_cast<int>(blockIdx.x) - src * per;
+    const int c = rem / tiles, h0 = (rem - c * tiles) * T;
+    const int64_t b = blockIdx.y, plane = b * g.C + c;
+    SP_DCHECK(src < 3 && c < g.C && h0 < g.H && N == g.W && g.W % 4 == 0);
+    const int64_t base = plane * g.H * g.W;
+    const float inv_a = 1.f / a;
+
+    phase_twiddles(tw, N);
+    const int groups = N / 4;
+    for (int idx = threadIdx.x; idx < T * groups; idx += kBlock) {
+        const int t = idx / groups, j = (idx - t * groups) * 4, h = h0 + t;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (h < g.H) {
+            SP_DCHECK(h * g.W + j + 4 <= g.H * g.W);
+            const int64_t off = base + h * g.W + j;
+            if (src == 0) {
+                float ev[4];
+                load_v<4>(x + off, v);
+                load_v<4>(eps + off, ev);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma clang fp contract(off)
+                    v[e] = (v[e] - k * ev[e]) * inv_a;
+                }
+            } else if (src == 1) {
+                load_v<4>(eps + off, v);
+            } else if constexpr (XI_IN) {
+                load_v<4>(xi + off, v);
+            } else {
+                philox_normals<4>(seed, step, sample_offset + b, off - b * g.C * g.H * g.W, v);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) A[t * NP + phase_slot(j + e)] = make_float2(v[e], 0.f);
+    }
+    __syncthreads();
+    const float2* res = phase_fft(A, B, tw, N, NP, T, false);
+    float2* __restrict__ wp = ws + src * stride + plane * (int64_t)g.HW * g.H;
+    const int total = T * g.HW;
+    for (int idx = threadIdx.x; idx < total; idx += kBlock) {
+        const int kw = idx / T, t = idx - kw * T, h = h0 + t;
+        if (h < g.H) {
+            SP_DCHECK(kw < g.HW && kw * g.H + h < g.HW * g.H);
+            wp[kw * g.H + h] = res[t * NP + phase_slot(kw)];
+        }
+    }
+}
+
+constexpr int kDdrmAcc = 8;  // frequencies of a column tile per thread: T * N <= 2000 < 8 * kBlock
+
+__global__ __launch_bounds__(kBlock) void k_pf_cols_ddrm(pf_geom g, float2* __restrict__ ws,
+                                                         int64_t stride, int T,
+                                                         const float2* __restrict__ qs, int64_t y_div,
+                                                         sp_ddrm_coefs cf) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int N = g.Nh, NP = phase_np(N);
+    float2* tw = reinterpret_cast<float2*>(smem);
+    float2* A = tw + N;
+    float2* B = A + T * NP;
+    const int tiles = (g.HW + T - 1) / T;
+    const int c = static_cast<int>(blockIdx.x) / tiles;
+    const int kw0 = (static_cast<int>(blockIdx.x) - c * tiles) * T;
+    const int64_t plane = (int64_t)blockIdx.y * g.C + c;
+    const int lines = min(T, g.HW - kw0), total = lines * N;
+    SP_DCHECK(c < g.C && kw0 < g.HW && N == g.H && total <= kDdrmAcc * kBlock);
+    const int64_t col0 = (plane * g.HW + kw0) * (int64_t)g.H;  // the tile's columns
+    const float2* __restrict__ msp = g.spec + (int64_t)kw0 * N;              // M
+    const float2* __restrict__ psp = msp + (int64_t)g.HW * N;                // P
+    const int64_t qplane = ((int64_t)blockIdx.y / y_div) * g.C + c;
+    const float2* __restrict__ qp = qs + (qplane * g.HW + kw0) * (int64_t)N;
+    const float sc = 1.f / ((float)g.Nh * (float)g.Nw);
+
+    phase_twiddles(tw, N);
+    float2 acc[kDdrmAcc];
+    float fth[kDdrmAcc], fep[kDdrmAcc], fxi[kDdrmAcc];
+#pragma unroll
+    for (int i = 0; i < kDdrmAcc; ++i) {
+#pragma clang fp contract(off)
+        const int idx = threadIdx.x + i * kBlock;
+        acc[i] = make_float2(0.f, 0.f);
+        fth[i] = fep[i] = fxi[i] = 0.f;
+        if (idx < total) {
+            const float2 m = msp[idx], pv = psp[idx], qv = qp[idx];
+            const float s2 = m.x * m.x + m.y * m.y;
+            const ddrm_f f = ddrm_class_coefs(cf, s2, pv.x != 0.f || pv.y != 0.f);
+            fth[i] = f.th * sc, fep[i] = f.ep * sc, fxi[i] = f.xi * sc;
+            acc[i] = make_float2(f.y * qv.x, f.y * qv.y);
+        }
+    }
+    for (int src = 0; src < 3; ++src) {
+        const float2* __restrict__ wp = ws + src * stride + col0;
+        if (src) __syncthreads();  // the last transform's result is read before A is staged again
+        for (int t = 0; t < T; ++t)
+            for (int q = threadIdx.x; q < N; q += kBlock) {
+                float2 val = make_float2(0.f, 0.f);
+                if (t < lines) {
+                    SP_DCHECK(q < g.H);
+                    val = wp[t * g.H + q];
+                }
+                A[t * NP + phase_slot(q)] = val;
+            }
+        __syncthreads();
+        const float2* z = phase_fft(A, B, tw, N, NP, T, false);
+#pragma unroll
+        for (int i = 0; i < kDdrmAcc; ++i) {
+#pragma clang fp contract(off)
+            const int idx = threadIdx.x + i * kBlock;
+            if (idx < total) {
+                const int t = idx / N, kh = idx - t * N;
+                const float2 v = z[t * NP + phase_slot(kh)];
+                const float f = src == 0 ? fth[i] : src == 1 ? fep[i] : fxi[i];
+                acc[i] = make_float2(acc[i].x + f * v.x, acc[i].y + f * v.y);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kDdrmAcc; ++i) {
+        const int idx = threadIdx.x + i * kBlock;
+        if (idx < total) {
+            const int t = idx / N, kh = idx - t * N;
+            A[t * NP + phase_slot(kh)] = acc[i];
+        }
+    }
+    __syncthreads();
+    const float2* u = phase_fft(A, B, tw, N, NP, T, true);
+    float2* __restrict__ w0 = ws + col0;
+    const int keep = lines * g.H;
+    for (int idx = threadIdx.x; idx < keep; idx += kBlock) {
+        const int t = idx / g.H, h = idx - t * g.H;
+        w0[idx] = u[t * NP + phase_slot(h)];
     }
 }
 
@@ -870,6 +1041,30 @@ int psf_periodic_prox(const sp_op* op, const prox_args& a, hipStream_t s) {
     if (rc == SP_OK)
         rc = pf_rows_prox(p, a.out,
                           {a.x, a.xi, nullptr, a.seed, a.step, a.sample_offset, a.c, a.eps != nullptr});
+    return rc;
+}
+
+// the DDRM step: three intermediates (x0, eps, xi), see k_pf_rows_ddrm
+int64_t psf_periodic_ddrm_workspace(const sp_op* op, int64_t batch) {
+    return 3 * psf_fft_workspace(op, batch);
+}
+
+int psf_periodic_ddrm(const sp_op* op, const ddrm_args& a, hipStream_t s) {
+    const pf_run p = pf_begin("sp_ddrm_step_ws", 0, op, PP_SPEC_M, a.batch, a.work, s);
+    const pf_geom& g = p.g;
+    const int64_t stride = psf_fft_workspace(op, a.batch) / 2;  // float2 of one intermediate
+    if ((int64_t)phase_lines(g.Nh) * g.Nh > (int64_t)kDdrmAcc * kBlock) return SP_EUNSUPPORTED;
+    const auto rows = a.xi ? k_pf_rows_ddrm<true> : k_pf_rows_ddrm<false>;
+    int rc = fft_stage(p.what, 0, 0.0, rows, 3 * g.C * pf_row_tiles(g), p.batch, g.Nw, s, g, a.x, a.eps,
+                       a.xi, a.seed, a.step, a.sample_offset, a.c.a, a.c.k, p.ws, stride,
+                       phase_lines(g.Nw));
+    if (rc == SP_OK)
+        rc = fft_stage(p.what, 0, 0.0, k_pf_cols_ddrm, g.C * pf_col_tiles(g), p.batch, g.Nh, s, g, p.ws,
+                       stride, phase_lines(g.Nh), reinterpret_cast<const float2*>(a.q), a.y_div, a.c);
+    if (rc == SP_OK)
+        rc = fft_stage(p.what, 0, 0.0, k_pf_rows_inv<PF_OUT_SCALE>, g.C * pf_row_tiles(g), p.batch, g.Nw,
+                       s, g, p.ws, a.out, kNoIn, (int64_t)1, a.c.a_prev, kNoOut, 0, phase_lines(g.Nw),
+                       kNoSched, kNoCursor, pf_prox_tail{});
     return rc;
 }
 

@@ -447,6 +447,94 @@ __global__ __launch_bounds__(kBlock) void k_sr_prox(sp_op op, const float* __res
     }
 }
 
+// The DDRM step (A A^T = I / s^2: every singular value is 1 / s, Pi = A^T A s^2 is the block mean
+// replicated), the projector form of samplers_hip.h in one launch next to k_sr_prox.  With
+// x0 = (x - k eps) / a, f = ddrm_class_coefs(c, 1 / s^2, true) (fo; fu the unobserved set's; both
+// taken once per launch on the host) and mean() the block mean (sums in the file comment's order,
+// 1 / s^2 exact):
+//   d  = (((f_th - 1) mean(x0) - (c1 sig_prev) mean(eps)) + (f_xi - eta sig_prev) mean(xi)) + f_y y
+//   x' = a_prev (((x0 + (c1 sig_prev) eps) + (eta sig_prev) xi) + d)
+// xi read, or drawn by Philox at the flat element index of every patch row.  A patch is read and
+// written by its own lane alone, so the output may alias x.  Bytes per element: 12 (x, eps read,
+// x' written) + 4 / s^2 (y), + 4 with xi injected.  Roundings of the longest path: x0 (4: 1 / a,
+// k eps, the difference, the product), the block sum (log2 s^2), f_th - 1 (5: f_th as in k_ddrm
+// and the difference) and its product (1), three sums of d (3), the sum with d (1), a_prev (1):
+// 15 + log2 s^2.
+template <int S, int PW, bool XI_IN>
+__global__ __launch_bounds__(kBlock) void k_sr_ddrm(sp_op op, const float* __restrict__ x,
+                                                    const float* __restrict__ eps,
+                                                    const float* __restrict__ y,
+                                                    const float* __restrict__ xi, uint64_t seed,
+                                                    int64_t step, int64_t sample_offset,
+                                                    int64_t y_div, sp_ddrm_coefs c, ddrm_f fo,
+                                                    ddrm_f fu, float* __restrict__ out) {
+    using cfg = sr_cfg<S, PW>;
+    const int64_t b = blockIdx.y, T = op.n / (S * PW);
+    const float* yb = y + (b / y_div) * op.m;
+    const float inv_a = 1.f / c.a;
+    const float g_th = fo.th - 1.f, g_xi = fo.xi - fu.xi;  // both round once
+#pragma unroll
+    for (int it = 0; it < cfg::kIter; ++it) {
+        const int64_t p = (int64_t)blockIdx.x * cfg::kTile + it * kBlock + threadIdx.x;
+        const bool in = p < T;  // pairs are in or out together (T and the tile base are even)
+        const sr_patch<S, PW> pt(op, in ? p : 0);
+        float xv[S][PW] = {}, ev[S][PW] = {}, nz[S][PW] = {}, yv[cfg::NY] = {};
+        if (in) {
+            sr_load<S, PW, true>(x + b * op.n, pt.xo, op.width, xv);
+            sr_load<S, PW, true>(eps + b * op.n, pt.xo, op.width, ev);
+            sr_load_y<cfg::NY>(yb, pt.yo, yv);
+            if constexpr (XI_IN) {
+                sr_load<S, PW>(xi + b * op.n, pt.xo, op.width, nz);
+            } else {
+#pragma unroll
+                for (int i = 0; i < S; ++i) {
+                    const int64_t j = pt.xo + (int64_t)i * op.width;  // flat element index of the row
+                    if constexpr (PW == 4) {
+                        SP_DCHECK(j % 4 == 0);
+                        philox_normals<4>(seed, step, sample_offset + b, j, nz[i]);
+                    } else {
+                        float q1[1];
+                        philox_normals<1>(seed, step, sample_offset + b, j, q1);
+                        nz[i][0] = q1[0];
+                        philox_normals<1>(seed, step, sample_offset + b, j + 1, q1);
+                        nz[i][1] = q1[0];
+                    }
+                }
+            }
+        }
+        // every product and sum of the step rounds on its own (no contraction): the bits are those
+        // of the expressions as written, whichever noise form the kernel was built for
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int e = 0; e < PW; ++e) {
+#pragma clang fp contract(off)
+                xv[i][e] = (xv[i][e] - c.k * ev[i][e]) * inv_a;  // x0
+            }
+        float s0[cfg::NY], se[cfg::NY], sx[cfg::NY], d[cfg::NY];
+        sr_block_sums<S, PW>(xv, s0);  // every lane of the wave: S = 8 exchanges half sums
+        sr_block_sums<S, PW>(ev, se);
+        sr_block_sums<S, PW>(nz, sx);
+#pragma unroll
+        for (int j = 0; j < cfg::NY; ++j) {
+#pragma clang fp contract(off)
+            d[j] = ((g_th * (s0[j] * cfg::kInv) - fu.ep * (se[j] * cfg::kInv)) +
+                    g_xi * (sx[j] * cfg::kInv)) +
+                   fo.y * yv[j];
+        }
+        if (!in) continue;
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int e = 0; e < PW; ++e) {
+#pragma clang fp contract(off)
+                xv[i][e] = c.a_prev * (((xv[i][e] + fu.ep * ev[i][e]) + fu.xi * nz[i][e]) +
+                                       d[sr_pixel_of<S, PW>(e)]);
+            }
+        sr_store<S, PW>(out + b * op.n, pt.xo, op.width, xv);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host side (called from the entry points in sp_dps.hip / sp_latent.hip; `op` is valid)
 // ---------------------------------------------------------------------------
@@ -550,6 +638,28 @@ int sr_prox(const sp_op* op, const prox_args& p, hipStream_t s) {
     else if (p.xi) sr_prox_launch<true, true>(op, p, s);
     else sr_prox_launch<true, false>(op, p, s);
     return check_launch(p.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws");
+}
+
+// the DDRM step: one launch over the blocks, xi read or drawn
+template <bool XI_IN>
+static void sr_ddrm_launch(const sp_op* op, const ddrm_args& p, hipStream_t s) {
+    const dim3 grid_(static_cast<unsigned>(sr_partials(op)), static_cast<unsigned>(p.batch));
+    const float g = 1.f / static_cast<float>(op->factor * op->factor);  // the squared singular value
+    const ddrm_f fo = ddrm_class_coefs(p.c, g, true), fu = ddrm_class_coefs(p.c, g, false);
+#define SR_DDRM_GO(S, PW)                                                                         \
+    launch(0, k_sr_ddrm<S, PW, XI_IN>, grid_, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, \
+           p.step, p.sample_offset, p.y_div, p.c, fo, fu, p.out)
+    if (!sr_vec(op)) SR_DDRM_GO(2, 2);
+    else if (op->factor == 2) SR_DDRM_GO(2, 4);
+    else if (op->factor == 4) SR_DDRM_GO(4, 4);
+    else SR_DDRM_GO(8, 4);
+#undef SR_DDRM_GO
+}
+
+int sr_ddrm(const sp_op* op, const ddrm_args& p, hipStream_t s) {
+    if (p.xi) sr_ddrm_launch<true>(op, p, s);
+    else sr_ddrm_launch<false>(op, p, s);
+    return check_launch("sp_ddrm_step_ws");
 }
 
 #undef SR_LAUNCH

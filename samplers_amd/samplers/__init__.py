@@ -1,4 +1,5 @@
 from .base import PosteriorSampler
+from .ddrm import DDRMSampler, FusedDDRMStep, ddrm_step_svd
 from .diffpir import DiffPIRSampler, FusedDiffPIRStep
 from .dps import DPSSampler, FusedDPSStep, KernelTimer
 from .pgdm import PGDMSampler
@@ -6,4 +7,5 @@ from .psld import FusedPSLDStep, PSLDSampler
 from .resample import ReSampleSampler
 
 __all__ = ["PosteriorSampler", "DPSSampler", "PSLDSampler", "PGDMSampler", "ReSampleSampler",
-           "DiffPIRSampler", "FusedDPSStep", "FusedDiffPIRStep", "FusedPSLDStep", "KernelTimer"]
+           "DiffPIRSampler", "DDRMSampler", "FusedDPSStep", "FusedDiffPIRStep", "FusedDDRMStep",
+           "FusedPSLDStep", "KernelTimer", "ddrm_step_svd"]

@@ -92,6 +92,36 @@ def diffpir_coefficients(acp: np.ndarray, t: int, t_prev: int, sigma: float,
                                f(k_prev * np.float64(zeta) ** 0.5))
 
 
+@dataclass(frozen=True)
+class DDRMCoefficients:
+    a: float         # sqrt(acp_t)
+    k: float         # sqrt(1 - acp_t)
+    a_prev: float    # sqrt(acp_prev)
+    sig_prev: float  # sqrt(1 - acp_prev) / sqrt(acp_prev): the VE noise level of the next sample
+    sig_y: float     # observation noise std
+    eta: float
+    eta_b: float
+    c1: float        # sqrt(1 - eta^2)
+
+
+def ddrm_coefficients(acp: np.ndarray, t: int, t_prev: int, sigma_y: float, eta: float = 0.85,
+                      eta_b: float = 1.0) -> DDRMCoefficients:
+    """fp32-rounded scalars of one DDRM step (Kawar et al. 2022, eq. 7-8 in the VP variables;
+    DESIGN.md §3).  ``a`` and ``k`` are ``x0_coefficients``; the others are computed in fp64 from
+    the fp32-rounded alphas, as ``diffpir_coefficients`` does."""
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    if not 0.0 <= float(eta_b) <= 1.0:
+        raise ValueError(f"eta_b must be in [0, 1], got {eta_b}")
+    if not (float(sigma_y) >= 0.0 and float(sigma_y) < float("inf")):
+        raise ValueError(f"sigma_y must be non-negative and finite, got {sigma_y}")
+    a, k = x0_coefficients(acp, t)
+    a_p = np.float64(np.float32(acp[t_prev]))
+    f = lambda v: float(np.float32(v))  # noqa: E731
+    return DDRMCoefficients(a, k, f(a_p ** 0.5), f((1 - a_p) ** 0.5 / a_p ** 0.5), f(sigma_y), f(eta),
+                            f(eta_b), f((1 - np.float64(eta) ** 2) ** 0.5))
+
+
 def compute_bridge_kernel_statistics(x_ell: Tensor, x_s: Tensor, epsilon_net: EpsilonNetwork,
                                      ell: int, t: int, s: int, eta: float = 1.0) -> BridgeStatistics:
     c = bridge_coefficients(host_alphas_cumprod(epsilon_net), ell, t, s, eta)
