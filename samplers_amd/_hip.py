@@ -423,6 +423,12 @@ def stream_of(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def descriptor_of(operator) -> "SpOp | None":
+    """The operator's HIP descriptor, or None for a plugin the library does not know."""
+    fn = getattr(operator, "hip_descriptor", None)
+    return None if fn is None else fn()
+
+
 def require_cuda(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise HipLibraryError(

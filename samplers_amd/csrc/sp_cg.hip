@@ -342,18 +342,12 @@ __global__ __launch_bounds__(kBlock) void k_cg_tail(const float* __restrict__ x0
             load_v<V>(d + b * n + j, dv);
             if constexpr (STEP) {
                 load_v<V>(x + b * n + j, xv);
-                if constexpr (XI_IN) load_v<V>(xi + b * n + j, nz);
-                else philox_normals<V>(seed, step, sample_offset + b, j, nz);
+                noise_v<V, XI_IN>(xi, seed, step, sample_offset, b, n, j, nz);
             }
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 const float z = iters > 0 ? x0v[e] + dv[e] : x0v[e];
-                if constexpr (STEP) {
-                    const float eh = (xv[e] - c.a * z) * inv_k;
-                    o[e] = c.a_prev * z + (c.c_eps * eh + c.c_xi * nz[e]);
-                } else {
-                    o[e] = z;
-                }
+                o[e] = STEP ? diffpir_update(c, inv_k, xv[e], z, nz[e]) : z;
             }
             store_v<V>(out + b * n + j, o);
         }
@@ -413,23 +407,15 @@ static int cg_run(const sp_op* op, const cg_args& a, hipStream_t s) {
             SP_CG_V(vn, k_cg_pupd, gn, blk, s, (const float*)L.g, n, L.Pn, (const cg_state*)L.st,
                     (const float*)L.part_g, L.p, L.part_p);
     }
-#define SP_CG_TAIL(V)                                                                             \
-    do {                                                                                          \
-        if (!step_form)                                                                           \
-            launch(0, k_cg_tail<V, false, false>, gn, blk, s, x0, (const float*)L.d, a.x, a.xi,   \
-                   a.seed, a.step, a.sample_offset, n, a.c, (const cg_state*)L.st, a.out,         \
-                   a.iters_out);                                                                  \
-        else if (a.xi)                                                                            \
-            launch(0, k_cg_tail<V, true, true>, gn, blk, s, x0, (const float*)L.d, a.x, a.xi,     \
-                   a.seed, a.step, a.sample_offset, n, a.c, (const cg_state*)L.st, a.out,         \
-                   a.iters_out);                                                                  \
-        else                                                                                      \
-            launch(0, k_cg_tail<V, true, false>, gn, blk, s, x0, (const float*)L.d, a.x, a.xi,    \
-                   a.seed, a.step, a.sample_offset, n, a.c, (const cg_state*)L.st, a.out,         \
-                   a.iters_out);                                                                  \
-    } while (0)
-    if (vn) SP_CG_TAIL(4); else SP_CG_TAIL(1);
-#undef SP_CG_TAIL
+    select_width(n, [&](auto v) {
+        select_bool(step_form, [&](auto step) {
+            select_bool(a.xi, [&](auto xin) {  // the prox form has no noise: one kernel
+                launch(0, k_cg_tail<v(), step(), step() && xin()>, gn, blk, s, x0, (const float*)L.d,
+                       a.x, a.xi, a.seed, a.step, a.sample_offset, n, a.c, (const cg_state*)L.st,
+                       a.out, a.iters_out);
+            });
+        });
+    });
     return check_launch(what);
 }
 #undef SP_CG_V

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/samplers_hip.h"
 
@@ -225,6 +226,61 @@ __device__ __forceinline__ uint32_t mask_bits(const sp_op& op, int64_t j) {
     return static_cast<uint32_t>(op.keep_bits[j >> 6] >> (j & 63)) & 0xFu;
 }
 
+// The observation tile of the elementwise kinds (IDENTITY / INPAINT / MASK): y of the kIter
+// groups of V elements a thread owns, 0 off the mask, behind the packed-row format.  issue()
+// goes inside the tile's load loop (the loads go out before any arithmetic), gather() after it.
+template <int OPK, int V>
+struct obs_tile {
+    float y[kIter][V];
+    uint32_t bits[kIter];
+    int64_t rank[kIter];
+
+    __device__ __forceinline__ void issue(const sp_op& op, const float* __restrict__ yb, int64_t j,
+                                          int it) {
+        if constexpr (OPK == SP_OP_INPAINT) {
+            inpaint_lookup(op, j, bits[it], rank[it]);
+        } else {
+            load_v<V>(yb + j, y[it]);
+            if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
+        }
+    }
+
+    // INPAINT: the rank walk over the packed row (kept pixels ascending); j0 is the thread's first
+    // element, as in the load loop
+    __device__ __forceinline__ void gather(const sp_op& op, const float* __restrict__ yb, int64_t j0) {
+        if constexpr (OPK == SP_OP_INPAINT) {
+#pragma unroll
+            for (int it = 0; it < kIter; ++it) {
+                const int64_t j = j0 + it * (kBlock * V);
+                if (j < op.n) {
+                    int64_t r = rank[it];
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        y[it][e] = 0.f;
+                        if ((bits[it] >> e) & 1u) y[it][e] = yb[r];
+                        r += (bits[it] >> e) & 1u;
+                    }
+                    SP_DCHECK(r <= op.m);  // packed observation index inside the row
+                }
+            }
+        }
+    }
+
+    __device__ __forceinline__ bool kept(int it, int e) const {
+        return OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+    }
+};
+
+// xi of elements j..j+V-1 of sample b (rows of n): read, or drawn by Philox at the flat element
+// index (keyed by seed, step, the global sample index sample_offset + b)
+template <int V, bool XI_IN>
+__device__ __forceinline__ void noise_v(const float* __restrict__ xi, uint64_t seed, int64_t step,
+                                        int64_t sample_offset, int64_t b, int64_t n, int64_t j,
+                                        float (&z)[V]) {
+    if constexpr (XI_IN) load_v<V>(xi + b * n + j, z);
+    else philox_normals<V>(seed, step, sample_offset + b, j, z);
+}
+
 // ---------------------------------------------------------------------------
 // Scalar pieces shared by the latent samplers' kernels (sp_latent.hip, sp_sr.hip)
 // ---------------------------------------------------------------------------
@@ -283,6 +339,24 @@ inline void launch_w(int kind, double work, K kernel, dim3 grid, dim3 block, hip
 template <typename K, typename... Args>
 inline void launch(int kind, K kernel, dim3 grid, dim3 block, hipStream_t s, Args... args) {
     launch_w(kind, 0.0, kernel, grid, block, s, args...);
+}
+
+// A run-time choice as a template argument: f is a generic lambda that gets the value as a
+// std::integral_constant and names the kernel instance with it.
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
+template <typename F>
+inline void select_bool(bool on, F&& f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// the vector width of rows of n floats: float4 groups where n % 4 == 0
+template <typename F>
+inline void select_width(int64_t n, F&& f) {
+    if (n % 4 == 0) f(int_c<4>{});
+    else f(int_c<1>{});
 }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -105,39 +105,19 @@ __global__ __launch_bounds__(kBlock) void k_dps_residual(sp_op op, const float* 
     float* vb = v + b * n;
     const int64_t j0 = (int64_t)blockIdx.x * kIter * (kBlock * V) + threadIdx.x * V;
     // issue every load of the tile first (memory-level parallelism), then compute
-    float xv[kIter][V], ev[kIter][V], yv[kIter][V];
-    uint32_t bits[kIter];
-    int64_t rank[kIter];
+    float xv[kIter][V], ev[kIter][V];
+    obs_tile<OPK, V> yt;
 #pragma unroll
     for (int it = 0; it < kIter; ++it) {
         const int64_t j = j0 + it * (kBlock * V);
         if (j < n) {
             load_v<V, SP_UPD_NT>(xb + j, xv[it]);
             load_v<V, SP_UPD_NT>(eb + j, ev[it]);
-            if constexpr (OPK == SP_OP_INPAINT) {
-                inpaint_lookup(op, j, bits[it], rank[it]);
-            } else {
-                load_v<V>(yb + j, yv[it]);
-                if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
-            }
+            yt.issue(op, yb, j, it);
         }
     }
-    if constexpr (OPK == SP_OP_INPAINT) {
-#pragma unroll
-        for (int it = 0; it < kIter; ++it) {
-            const int64_t j = j0 + it * (kBlock * V);
-            if (j < n) {
-                int64_t r = rank[it];
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    yv[it][e] = 0.f;
-                    if ((bits[it] >> e) & 1u) yv[it][e] = yb[r];
-                    r += (bits[it] >> e) & 1u;
-                }
-                SP_DCHECK(r <= op.m);  // packed observation index inside the row
-            }
-        }
-    }
+    yt.gather(op, yb, j0);
+    const auto& yv = yt.y;
     float acc = 0.f;
 #pragma unroll
     for (int it = 0; it < kIter; ++it) {
@@ -146,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_dps_residual(sp_op op, const float* 
             float vv[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                const bool kept = OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+                const bool kept = yt.kept(it, e);
                 const float x0 = (xv[it][e] - k * ev[it][e]) / a;
                 // MASK: unobserved pixels still add y^2 to the residual (A x0 = 0 there)
                 const float r = yv[it][e] - (kept ? x0 : 0.f);
@@ -192,9 +172,9 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_dps_update(
     const float* yb = y + (b / y_div) * op.m;
     float* ob = xo + b * n;
     const int64_t j0 = (int64_t)blockIdx.x * kIter * (kBlock * V) + threadIdx.x * V;
-    float xv[kIter][V], ev[kIter][V], wv[kIter][V], yv[kIter][V];
-    uint32_t bits[kIter];
-    int64_t rank[kIter];
+    float xv[kIter][V], ev[kIter][V], wv[kIter][V];
+    obs_tile<OPK, V> yt;
+    auto& yv = yt.y;
 #pragma unroll
     for (int it = 0; it < kIter; ++it) {
         const int64_t j = j0 + it * (kBlock * V);
@@ -204,30 +184,12 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_dps_update(
             load_v<V, SP_UPD_NT>(wb + j, wv[it]);
             if constexpr (V_IN) {
                 load_v<V, SP_UPD_NT>(v + b * n + j, yv[it]);  // yv holds v in this variant
-            } else if constexpr (OPK == SP_OP_INPAINT) {
-                inpaint_lookup(op, j, bits[it], rank[it]);
             } else {
-                load_v<V>(yb + j, yv[it]);
-                if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
+                yt.issue(op, yb, j, it);
             }
         }
     }
-    if constexpr (!V_IN && OPK == SP_OP_INPAINT) {
-#pragma unroll
-        for (int it = 0; it < kIter; ++it) {
-            const int64_t j = j0 + it * (kBlock * V);
-            if (j < n) {
-                int64_t r = rank[it];
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    yv[it][e] = 0.f;
-                    if ((bits[it] >> e) & 1u) yv[it][e] = yb[r];
-                    r += (bits[it] >> e) & 1u;
-                }
-                SP_DCHECK(r <= op.m);
-            }
-        }
-    }
+    if constexpr (!V_IN) yt.gather(op, yb, j0);
     SP_DCHECK(!partial || P > 0);
     const float inv_a = 1.f / c.a;
     // DPS: gamma / (||r_b|| + eps); without partials a fixed factor (PGDM, PSLD)
@@ -239,11 +201,7 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_dps_update(
         const int64_t j = j0 + it * (kBlock * V);
         if (j < n) {
             float z[V];
-            if constexpr (XI_IN) {
-                load_v<V>(xi + b * n + j, z);
-            } else {
-                philox_normals<V>(seed, step, sample_offset + b, j, z);
-            }
+            noise_v<V, XI_IN>(xi, seed, step, sample_offset, b, n, j, z);
             float out[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
@@ -253,7 +211,7 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_dps_update(
                 if constexpr (V_IN) {
                     vv = yv[it][e];
                 } else {
-                    const bool kept = OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+                    const bool kept = yt.kept(it, e);
                     vv = kept ? c.grad_scale * (yv[it][e] - x0) : 0.f;
                 }
                 const float mean = c.c_ell * xv[it][e] + c.c_s * x0;
@@ -288,9 +246,8 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_prox(
     const float* yb = y + (b / y_div) * op.m;
     float* ob = out + b * n;
     const int64_t j0 = (int64_t)blockIdx.x * kIter * (kBlock * V) + threadIdx.x * V;
-    float xv[kIter][V], ev[kIter][V], yv[kIter][V];
-    uint32_t bits[kIter];
-    int64_t rank[kIter];
+    float xv[kIter][V], ev[kIter][V];
+    obs_tile<OPK, V> yt;
 #pragma unroll
     for (int it = 0; it < kIter; ++it) {
         const int64_t j = j0 + it * (kBlock * V);
@@ -298,30 +255,11 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_prox(
             SP_DCHECK(j + V <= n);
             load_v<V, SP_UPD_NT>(xb + j, xv[it]);
             if constexpr (STEP) load_v<V, SP_UPD_NT>(eb + j, ev[it]);
-            if constexpr (OPK == SP_OP_INPAINT) {
-                inpaint_lookup(op, j, bits[it], rank[it]);
-            } else {
-                load_v<V>(yb + j, yv[it]);
-                if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
-            }
+            yt.issue(op, yb, j, it);
         }
     }
-    if constexpr (OPK == SP_OP_INPAINT) {
-#pragma unroll
-        for (int it = 0; it < kIter; ++it) {
-            const int64_t j = j0 + it * (kBlock * V);
-            if (j < n) {
-                int64_t r = rank[it];
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    yv[it][e] = 0.f;
-                    if ((bits[it] >> e) & 1u) yv[it][e] = yb[r];
-                    r += (bits[it] >> e) & 1u;
-                }
-                SP_DCHECK(r <= op.m);  // packed observation index inside the row
-            }
-        }
-    }
+    yt.gather(op, yb, j0);
+    const auto& yv = yt.y;
     const float inv_d = 1.f / (1.f + c.rho);
     const float inv_a = STEP ? 1.f / c.a : 1.f, inv_k = STEP ? 1.f / c.k : 1.f;
 #pragma unroll
@@ -329,25 +267,17 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_prox(
         const int64_t j = j0 + it * (kBlock * V);
         if (j < n) {
             float nz[V] = {};
-            if constexpr (STEP) {
-                if constexpr (XI_IN) load_v<V>(xi + b * n + j, nz);
-                else philox_normals<V>(seed, step, sample_offset + b, j, nz);
-            }
+            if constexpr (STEP) noise_v<V, XI_IN>(xi, seed, step, sample_offset, b, n, j, nz);
             float o[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
 // every product and sum below rounds on its own: the bits are those of the expression as written,
 // whichever noise form the kernel was built for
 #pragma clang fp contract(off)
-                const bool kept = OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+                const bool kept = yt.kept(it, e);
                 const float x0 = STEP ? (xv[it][e] - c.k * ev[it][e]) * inv_a : xv[it][e];
                 const float z = kept ? x0 + (yv[it][e] - x0) * inv_d : x0;
-                if constexpr (STEP) {
-                    const float eh = (xv[it][e] - c.a * z) * inv_k;
-                    o[e] = c.a_prev * z + (c.c_eps * eh + c.c_xi * nz[e]);
-                } else {
-                    o[e] = z;
-                }
+                o[e] = STEP ? diffpir_update(c, inv_k, xv[it][e], z, nz[e]) : z;
             }
             store_v<V, STEP>(ob + j, o);
         }
@@ -379,9 +309,8 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_ddrm(
     const float* yb = y + (b / y_div) * op.m;
     float* ob = out + b * n;
     const int64_t j0 = (int64_t)blockIdx.x * kIter * (kBlock * V) + threadIdx.x * V;
-    float xv[kIter][V], ev[kIter][V], yv[kIter][V];
-    uint32_t bits[kIter];
-    int64_t rank[kIter];
+    float xv[kIter][V], ev[kIter][V];
+    obs_tile<OPK, V> yt;
 #pragma unroll
     for (int it = 0; it < kIter; ++it) {
         const int64_t j = j0 + it * (kBlock * V);
@@ -389,44 +318,24 @@ __global__ __launch_bounds__(kBlock, SP_UPD_WAVES) void k_ddrm(
             SP_DCHECK(j + V <= n);
             load_v<V, SP_UPD_NT>(xb + j, xv[it]);
             load_v<V, SP_UPD_NT>(eb + j, ev[it]);
-            if constexpr (OPK == SP_OP_INPAINT) {
-                inpaint_lookup(op, j, bits[it], rank[it]);
-            } else {
-                load_v<V>(yb + j, yv[it]);
-                if constexpr (OPK == SP_OP_MASK) bits[it] = mask_bits(op, j);
-            }
+            yt.issue(op, yb, j, it);
         }
     }
-    if constexpr (OPK == SP_OP_INPAINT) {
-#pragma unroll
-        for (int it = 0; it < kIter; ++it) {
-            const int64_t j = j0 + it * (kBlock * V);
-            if (j < n) {
-                int64_t r = rank[it];
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    yv[it][e] = 0.f;
-                    if ((bits[it] >> e) & 1u) yv[it][e] = yb[r];
-                    r += (bits[it] >> e) & 1u;
-                }
-                SP_DCHECK(r <= op.m);  // packed observation index inside the row
-            }
-        }
-    }
+    yt.gather(op, yb, j0);
+    const auto& yv = yt.y;
     const float inv_a = 1.f / c.a;
 #pragma unroll
     for (int it = 0; it < kIter; ++it) {
         const int64_t j = j0 + it * (kBlock * V);
         if (j < n) {
             float nz[V];
-            if constexpr (XI_IN) load_v<V>(xi + b * n + j, nz);
-            else philox_normals<V>(seed, step, sample_offset + b, j, nz);
+            noise_v<V, XI_IN>(xi, seed, step, sample_offset, b, n, j, nz);
             float o[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
 // every product and sum rounds on its own: the bits of the expression as written, in both noise forms
 #pragma clang fp contract(off)
-                const bool kept = OPK == SP_OP_IDENTITY || ((bits[it] >> e) & 1u);
+                const bool kept = yt.kept(it, e);
                 const float x0 = (xv[it][e] - c.k * ev[it][e]) * inv_a;
                 o[e] = kept ? c.a_prev * ((fo.th * x0 + fo.y * yv[it][e]) + fo.xi * nz[e])
                             : c.a_prev * ((x0 + fu.ep * ev[it][e]) + fu.xi * nz[e]);
@@ -565,19 +474,25 @@ static bool mask_valid(const sp_op* op) { return op->keep_bits && op->m == op->n
 
 static int64_t elementwise_partials(const sp_op* op) { return tiles_elementwise(op->n); }
 
+// f(kind, width) for the elementwise kernel of `kind` over rows of n floats (select_width)
+template <typename F>
+static void select_elementwise(int kind, int64_t n, F&& f) {
+    select_width(n, [&](auto v) {
+        switch (kind) {
+            case SP_OP_IDENTITY: f(int_c<SP_OP_IDENTITY>{}, v); break;
+            case SP_OP_MASK: f(int_c<SP_OP_MASK>{}, v); break;
+            default: f(int_c<SP_OP_INPAINT>{}, v); break;
+        }
+    });
+}
+
 static int elementwise_dps_residual(const sp_op* op, const dps_residual_args& r, hipStream_t s) {
     const int P = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(P, static_cast<unsigned>(r.batch));
-    const bool v4 = op->n % 4 == 0;
-#define SP_K1(OPK, V)                                                                       \
-    launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_dps_residual<OPK, V>, grid, dim3(kBlock), s, *op, r.x, r.eps, r.y, \
-           r.y_div, r.a, r.k, r.gs, r.v, r.partial, P, r.sched, r.cursor)
-    switch (op->kind) {
-        case SP_OP_IDENTITY: if (v4) SP_K1(SP_OP_IDENTITY, 4); else SP_K1(SP_OP_IDENTITY, 1); break;
-        case SP_OP_MASK: if (v4) SP_K1(SP_OP_MASK, 4); else SP_K1(SP_OP_MASK, 1); break;
-        default: if (v4) SP_K1(SP_OP_INPAINT, 4); else SP_K1(SP_OP_INPAINT, 1); break;
-    }
-#undef SP_K1
+    select_elementwise(op->kind, op->n, [&](auto opk, auto v) {
+        launch_w(TK_DPS_RESIDUAL, (double)r.batch, k_dps_residual<opk(), v()>, grid, dim3(kBlock), s,
+                 *op, r.x, r.eps, r.y, r.y_div, r.a, r.k, r.gs, r.v, r.partial, P, r.sched, r.cursor);
+    });
     return check_launch("sp_dps_residual");
 }
 
@@ -606,107 +521,99 @@ static int elementwise_map(const sp_op* op, const float* in, float* out, int64_t
 // the proximal data step, alone (p.eps null) or inside the DiffPIR step: one launch of K3
 static int elementwise_prox(const sp_op* op, const prox_args& p, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>(tiles_elementwise(op->n)), static_cast<unsigned>(p.batch));
-    const bool v4 = op->n % 4 == 0;
-#define SP_K3(OPK, V, STEP, XIN)                                                              \
-    launch(0, k_prox<OPK, V, STEP, XIN>, grid, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, \
-           p.step, p.sample_offset, p.y_div, p.c, p.out)
-#define SP_K3_FORM(OPK, V)                                  \
-    if (!p.eps) SP_K3(OPK, V, false, false);                \
-    else if (p.xi) SP_K3(OPK, V, true, true);               \
-    else SP_K3(OPK, V, true, false)
-#define SP_K3_V(OPK) \
-    if (v4) { SP_K3_FORM(OPK, 4); } else { SP_K3_FORM(OPK, 1); }
-    switch (op->kind) {
-        case SP_OP_IDENTITY: SP_K3_V(SP_OP_IDENTITY) break;
-        case SP_OP_MASK: SP_K3_V(SP_OP_MASK) break;
-        default: SP_K3_V(SP_OP_INPAINT) break;
-    }
-#undef SP_K3_V
-#undef SP_K3_FORM
-#undef SP_K3
+    select_elementwise(op->kind, op->n, [&](auto opk, auto v) {
+        select_bool(p.eps, [&](auto step) {
+            select_bool(p.xi, [&](auto xin) {  // the prox form has no noise: one kernel
+                launch(0, k_prox<opk(), v(), step(), step() && xin()>, grid, dim3(kBlock), s, *op, p.x,
+                       p.eps, p.y, p.xi, p.seed, p.step, p.sample_offset, p.y_div, p.c, p.out);
+            });
+        });
+    });
     return check_launch(p.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws");
 }
 
 // the DDRM step of the elementwise kinds: one launch of K4
 static int elementwise_ddrm(const sp_op* op, const ddrm_args& p, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>(tiles_elementwise(op->n)), static_cast<unsigned>(p.batch));
-    const bool v4 = op->n % 4 == 0;
     const ddrm_f fo = ddrm_class_coefs(p.c, 1.f, true), fu = ddrm_class_coefs(p.c, 1.f, false);
-#define SP_K4(OPK, V, XIN)                                                                      \
-    launch(0, k_ddrm<OPK, V, XIN>, grid, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, p.step, \
-           p.sample_offset, p.y_div, p.c, fo, fu, p.out)
-#define SP_K4_FORM(OPK, V)         \
-    if (p.xi) SP_K4(OPK, V, true); \
-    else SP_K4(OPK, V, false)
-#define SP_K4_V(OPK) \
-    if (v4) { SP_K4_FORM(OPK, 4); } else { SP_K4_FORM(OPK, 1); }
-    switch (op->kind) {
-        case SP_OP_IDENTITY: SP_K4_V(SP_OP_IDENTITY) break;
-        case SP_OP_MASK: SP_K4_V(SP_OP_MASK) break;
-        default: SP_K4_V(SP_OP_INPAINT) break;
-    }
-#undef SP_K4_V
-#undef SP_K4_FORM
-#undef SP_K4
+    select_elementwise(op->kind, op->n, [&](auto opk, auto v) {
+        select_bool(p.xi, [&](auto xin) {
+            launch(0, k_ddrm<opk(), v(), xin()>, grid, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi,
+                   p.seed, p.step, p.sample_offset, p.y_div, p.c, fo, fu, p.out);
+        });
+    });
     return check_launch("sp_ddrm_step_ws");
 }
 
-// The dispatch table: one row per kind, indexed by sp_op.kind (sp_ops.h)
-#define SP_ELEMENTWISE_ROW(VALID)                                                              \
-    {VALID, elementwise_partials, nullptr, nullptr, elementwise_dps_residual,                  \
-     elementwise_map<false>, elementwise_map<true>, nullptr, nullptr, elementwise_psld_pixel,  \
-     elementwise_psld_cotangent, elementwise_pixel_opt, SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, \
-     nullptr, nullptr, nullptr, nullptr, nullptr, elementwise_prox, elementwise_prox, nullptr,     \
-     elementwise_ddrm}
-static const op_kind g_kinds[] = {
-    /* SP_OP_IDENTITY */ SP_ELEMENTWISE_ROW(identity_valid),
-    /* SP_OP_INPAINT */ SP_ELEMENTWISE_ROW(inpaint_valid),
+// The dispatch table: one row per kind, indexed by sp_op.kind (sp_ops.h).  Members are named, in
+// op_kind's order; one a row leaves out is null.
+static constexpr op_kind elementwise_row(valid_fn* valid) {
+    return {.valid = valid, .partials = elementwise_partials,
+            .dps_residual = elementwise_dps_residual, .apply = elementwise_map<false>,
+            .adjoint = elementwise_map<true>, .psld_pixel = elementwise_psld_pixel,
+            .psld_cotangent = elementwise_psld_cotangent, .pixel_opt = elementwise_pixel_opt,
+            .traits = SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, .prox = elementwise_prox,
+            .diffpir_step = elementwise_prox, .ddrm_step = elementwise_ddrm};
+}
+static constexpr op_kind g_kinds[] = {
+    /* SP_OP_IDENTITY */ elementwise_row(identity_valid),
+    /* SP_OP_INPAINT */ elementwise_row(inpaint_valid),
     /* SP_OP_BLUR: no fused latent pass (its adjoint needs a halo), A^T A u from the caller */
-    {blur_valid, blur_partials, nullptr, nullptr, blur_dps_residual, blur_apply, blur_adjoint,
-     nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
-    /* SP_OP_MASK */ SP_ELEMENTWISE_ROW(mask_valid),
+    {.valid = blur_valid, .partials = blur_partials, .dps_residual = blur_dps_residual,
+     .apply = blur_apply, .adjoint = blur_adjoint, .psld_cotangent = elementwise_psld_cotangent,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
+    /* SP_OP_MASK */ elementwise_row(mask_valid),
     /* SP_OP_SR */
-    {sr_valid, sr_partials, nullptr, nullptr, sr_dps_residual, sr_apply, sr_adjoint, nullptr,
-     nullptr, sr_psld_pixel, sr_psld_cotangent, sr_pixel_opt,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, nullptr, nullptr, nullptr,
-     nullptr, nullptr, sr_prox, sr_prox, nullptr, sr_ddrm},
+    {.valid = sr_valid, .partials = sr_partials, .dps_residual = sr_dps_residual, .apply = sr_apply,
+     .adjoint = sr_adjoint, .psld_pixel = sr_psld_pixel, .psld_cotangent = sr_psld_cotangent,
+     .pixel_opt = sr_pixel_opt,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_FUSED_LATENT | SP_TRAIT_LINEAR, .prox = sr_prox,
+     .diffpir_step = sr_prox, .ddrm_step = sr_ddrm},
     /* SP_OP_PSF: as BLUR, and two launches through the caller's work buffer (_ws forms) */
-    {psf_valid, psf_partials, psf_workspace, nullptr, psf_dps_residual, psf_apply, psf_adjoint,
-     nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
+    {.valid = psf_valid, .partials = psf_partials, .dps_workspace = psf_workspace,
+     .dps_residual = psf_dps_residual, .apply = psf_apply, .adjoint = psf_adjoint,
+     .psld_cotangent = elementwise_psld_cotangent,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
     /* SP_OP_PHASE: nonlinear (no adjoint, no A^T A, no PSLD), three launches through work */
-    {phase_valid, phase_partials, phase_workspace, phase_workspace, phase_dps_residual, nullptr,
-     nullptr, phase_apply, phase_vjp, nullptr, nullptr, nullptr,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
+    {.valid = phase_valid, .partials = phase_partials, .dps_workspace = phase_workspace,
+     .op_workspace = phase_workspace, .dps_residual = phase_dps_residual, .apply_ws = phase_apply,
+     .vjp_ws = phase_vjp, .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
     /* SP_OP_PSF_FFT: linear, but its maps need the workspace: apply_ws = A, vjp_ws = A^T (x not
        read); five pass-1 launches through work; no sp_op_apply / _adjoint, no latent passes */
-    {psf_fft_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace, psf_fft_dps_residual,
-     nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr, nullptr, nullptr,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
+    {.valid = psf_fft_valid, .partials = psf_fft_partials, .dps_workspace = psf_fft_workspace,
+     .op_workspace = psf_fft_workspace, .dps_residual = psf_fft_dps_residual,
+     .apply_ws = psf_fft_apply, .vjp_ws = psf_fft_vjp,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE},
     /* SP_OP_PSF_PERIODIC: PSF_FFT's functions on exact-size transforms (nothing extended or
        folded), and the only kind with the pseudo-inverse columns: A^+, the PGDM pass 1; its
        proximal map is one more multiplier between the column transforms */
-    {psf_periodic_valid, psf_fft_partials, psf_fft_workspace, psf_fft_workspace,
-     psf_fft_dps_residual, nullptr, nullptr, psf_fft_apply, psf_fft_vjp, nullptr,
-     nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
-     psf_periodic_pinv, psf_periodic_pgdm_prepare, psf_periodic_pgdm_residual,
-     psf_fft_workspace, psf_periodic_prox_prepare, psf_periodic_prox, psf_periodic_prox,
-     psf_periodic_ddrm_workspace, psf_periodic_ddrm},
+    {.valid = psf_periodic_valid, .partials = psf_fft_partials, .dps_workspace = psf_fft_workspace,
+     .op_workspace = psf_fft_workspace, .dps_residual = psf_fft_dps_residual,
+     .apply_ws = psf_fft_apply, .vjp_ws = psf_fft_vjp,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
+     .pinv_ws = psf_periodic_pinv, .pgdm_prepare = psf_periodic_pgdm_prepare,
+     .pgdm_residual = psf_periodic_pgdm_residual, .prox_workspace = psf_fft_workspace,
+     .prox_prepare = psf_periodic_prox_prepare, .prox = psf_periodic_prox,
+     .diffpir_step = psf_periodic_prox, .ddrm_workspace = psf_periodic_ddrm_workspace,
+     .ddrm_step = psf_periodic_ddrm},
     /* SP_OP_RADON: as PSF (project, then backproject through the caller's work buffer), with an
        observation space of its own geometry: m = channels * radius * factor */
-    {radon_valid, radon_partials, radon_workspace, nullptr, radon_dps_residual, radon_apply,
-     radon_adjoint, nullptr, nullptr, nullptr, elementwise_psld_cotangent, nullptr,
-     SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
+    {.valid = radon_valid, .partials = radon_partials, .dps_workspace = radon_workspace,
+     .dps_residual = radon_dps_residual, .apply = radon_apply, .adjoint = radon_adjoint,
+     .psld_cotangent = elementwise_psld_cotangent,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U},
     /* SP_OP_SR_PERIODIC: the periodic kind's columns with a lattice between the transforms: every
        pass PSF_PERIODIC has, y of (C, H / s, W / s) */
-    {sr_periodic_valid, sr_periodic_partials, psf_fft_workspace, psf_fft_workspace,
-     sr_periodic_dps_residual, nullptr, nullptr, sr_periodic_apply, sr_periodic_vjp, nullptr,
-     nullptr, nullptr, SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
-     sr_periodic_pinv, sr_periodic_pgdm_prepare, sr_periodic_pgdm_residual, psf_fft_workspace,
-     sr_periodic_prox_prepare, sr_periodic_prox, sr_periodic_prox},
+    {.valid = sr_periodic_valid, .partials = sr_periodic_partials,
+     .dps_workspace = psf_fft_workspace, .op_workspace = psf_fft_workspace,
+     .dps_residual = sr_periodic_dps_residual, .apply_ws = sr_periodic_apply,
+     .vjp_ws = sr_periodic_vjp,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
+     .pinv_ws = sr_periodic_pinv, .pgdm_prepare = sr_periodic_pgdm_prepare,
+     .pgdm_residual = sr_periodic_pgdm_residual, .prox_workspace = psf_fft_workspace,
+     .prox_prepare = sr_periodic_prox_prepare, .prox = sr_periodic_prox,
+     .diffpir_step = sr_periodic_prox},
 };
-#undef SP_ELEMENTWISE_ROW
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
@@ -871,26 +778,16 @@ static int dps_update_impl(const sp_op* op, const float* x, const float* eps, co
     const int P = static_cast<int>(sp_rsq_partials(op));
     const int Pw = static_cast<int>(tiles_elementwise(op->n));
     const dim3 grid(Pw, static_cast<unsigned>(batch));
-    const bool v4 = op->n % 4 == 0;
     // kinds that read v: the identity-kind kernel over it (flat Philox element index)
-    const int opk = reads_v ? SP_OP_IDENTITY : op->kind;
-#define SP_K2(OPK, V, VIN, XIN)                                                            \
-    launch_w(TK_DPS_UPDATE, (double)batch, k_dps_update<OPK, V, VIN, XIN>, grid, dim3(kBlock), s, *op, x, eps, y, \
-           v, w, rsq_partial, P, xi, seed, step, sample_offset, y_div, c, x_out, sched, cursor)
-#define SP_K2_XI(OPK, V, VIN) \
-    if (xi) SP_K2(OPK, V, VIN, true); else SP_K2(OPK, V, VIN, false)
-#define SP_K2_V(OPK, V) \
-    if (v) { SP_K2_XI(OPK, V, true); } else { SP_K2_XI(OPK, V, false); }
-    if (opk == SP_OP_IDENTITY) {
-        if (v4) { SP_K2_V(SP_OP_IDENTITY, 4) } else { SP_K2_V(SP_OP_IDENTITY, 1) }
-    } else if (opk == SP_OP_MASK) {
-        if (v4) { SP_K2_V(SP_OP_MASK, 4) } else { SP_K2_V(SP_OP_MASK, 1) }
-    } else {
-        if (v4) { SP_K2_V(SP_OP_INPAINT, 4) } else { SP_K2_V(SP_OP_INPAINT, 1) }
-    }
-#undef SP_K2_V
-#undef SP_K2_XI
-#undef SP_K2
+    select_elementwise(reads_v ? SP_OP_IDENTITY : op->kind, op->n, [&](auto opk, auto vw) {
+        select_bool(v, [&](auto vin) {
+            select_bool(xi, [&](auto xin) {
+                launch_w(TK_DPS_UPDATE, (double)batch, k_dps_update<opk(), vw(), vin(), xin()>, grid,
+                         dim3(kBlock), s, *op, x, eps, y, v, w, rsq_partial, P, xi, seed, step,
+                         sample_offset, y_div, c, x_out, sched, cursor);
+            });
+        });
+    });
     return check_launch("sp_dps_update");
 }
 

@@ -59,6 +59,17 @@ __host__ __device__ inline ddrm_f ddrm_class_coefs(const sp_ddrm_coefs& c, float
     return {1.f - r, 0.f, r, es};
 }
 
+// The DiffPIR update from the proximal point z: eps_hat = (x - a z) / k (inv_k = 1 / k, taken once
+// per thread) and x' = a_prev z + (c_eps eps_hat + c_xi xi).  Every product and sum rounds on its
+// own: the bits are those of the expressions as written, whichever noise form the kernel was built
+// for.  The pragma is lexical, so it stands here and not only at the call sites.
+__host__ __device__ inline float diffpir_update(const sp_prox_coefs& c, float inv_k, float x, float z,
+                                                float xi) {
+#pragma clang fp contract(off)
+    const float eh = (x - c.a * z) * inv_k;
+    return c.a_prev * z + (c.c_eps * eh + c.c_xi * xi);
+}
+
 typedef bool valid_fn(const sp_op* op);
 typedef int64_t partials_fn(const sp_op* op);
 typedef int64_t workspace_fn(const sp_op* op, int64_t batch);

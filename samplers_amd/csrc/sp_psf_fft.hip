@@ -387,8 +387,7 @@ __global__ __launch_bounds__(kBlock) void k_pf_rows_inv(pf_geom g, float2* __res
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
 #pragma clang fp contract(off)  // the bits of the expression as written, in both noise forms
-                    const float eh = (xv[e] - px.c.a * o[e]) * inv_k;
-                    o[e] = px.c.a_prev * o[e] + (px.c.c_eps * eh + px.c.c_xi * nz[e]);
+                    o[e] = diffpir_update(px.c, inv_k, xv[e], o[e], nz[e]);
                 }
             }
             store_v<4>(op_out + h * g.W + j, o);

@@ -364,6 +364,24 @@ __global__ __launch_bounds__(kBlock) void k_sr_pixel_opt(sp_op op, float* __rest
     if (threadIdx.x == 0) partial[b * P + blockIdx.x] = t;
 }
 
+// xi of one patch row, PW elements from flat element index j of sample b: noise_v's forms.  A
+// PW = 2 row starts at any even j, so its two elements are read or drawn one by one.
+template <int PW, bool XI_IN>
+__device__ __forceinline__ void sr_row_noise(const float* __restrict__ xi, uint64_t seed,
+                                             int64_t step, int64_t sample_offset, int64_t b,
+                                             int64_t n, int64_t j, float (&nz)[PW]) {
+    if constexpr (PW == 4) {
+        SP_DCHECK(j % 4 == 0);
+        noise_v<4, XI_IN>(xi, seed, step, sample_offset, b, n, j, nz);
+    } else {
+        float q1[1];
+        noise_v<1, XI_IN>(xi, seed, step, sample_offset, b, n, j, q1);
+        nz[0] = q1[0];
+        noise_v<1, XI_IN>(xi, seed, step, sample_offset, b, n, j + 1, q1);
+        nz[1] = q1[0];
+    }
+}
+
 // The proximal data step (A A^T = I / s^2): z = x0 + (r replicated over its block) / (1 + rho s^2)
 // with r = y - (block mean of x0, summed in the file comment's order).  STEP false
 // (sp_op_prox_ws): x holds x0, z is written.  STEP true (sp_diffpir_step_ws):
@@ -417,30 +435,13 @@ __global__ __launch_bounds__(kBlock) void k_sr_prox(sp_op op, const float* __res
             float nz[PW] = {};
             if constexpr (STEP) {
                 const int64_t j = pt.xo + (int64_t)i * op.width;  // flat element index of the row
-                if constexpr (XI_IN) {
-                    if constexpr (PW == 4) load_v<4>(xi + b * op.n + j, nz);
-                    else nz[0] = xi[b * op.n + j], nz[1] = xi[b * op.n + j + 1];
-                } else if constexpr (PW == 4) {
-                    SP_DCHECK(j % 4 == 0);
-                    philox_normals<4>(seed, step, sample_offset + b, j, nz);
-                } else {
-                    float q1[1];
-                    philox_normals<1>(seed, step, sample_offset + b, j, q1);
-                    nz[0] = q1[0];
-                    philox_normals<1>(seed, step, sample_offset + b, j + 1, q1);
-                    nz[1] = q1[0];
-                }
+                sr_row_noise<PW, XI_IN>(xi, seed, step, sample_offset, b, op.n, j, nz);
             }
 #pragma unroll
             for (int e = 0; e < PW; ++e) {
 #pragma clang fp contract(off)
                 const float z = zv[i][e] + d[sr_pixel_of<S, PW>(e)];
-                if constexpr (STEP) {
-                    const float eh = (xv[i][e] - c.a * z) * inv_k;
-                    zv[i][e] = c.a_prev * z + (c.c_eps * eh + c.c_xi * nz[e]);
-                } else {
-                    zv[i][e] = z;
-                }
+                zv[i][e] = STEP ? diffpir_update(c, inv_k, xv[i][e], z, nz[e]) : z;
             }
         }
         sr_store<S, PW>(out + b * op.n, pt.xo, op.width, zv);
@@ -483,23 +484,10 @@ __global__ __launch_bounds__(kBlock) void k_sr_ddrm(sp_op op, const float* __res
             sr_load<S, PW, true>(x + b * op.n, pt.xo, op.width, xv);
             sr_load<S, PW, true>(eps + b * op.n, pt.xo, op.width, ev);
             sr_load_y<cfg::NY>(yb, pt.yo, yv);
-            if constexpr (XI_IN) {
-                sr_load<S, PW>(xi + b * op.n, pt.xo, op.width, nz);
-            } else {
 #pragma unroll
-                for (int i = 0; i < S; ++i) {
-                    const int64_t j = pt.xo + (int64_t)i * op.width;  // flat element index of the row
-                    if constexpr (PW == 4) {
-                        SP_DCHECK(j % 4 == 0);
-                        philox_normals<4>(seed, step, sample_offset + b, j, nz[i]);
-                    } else {
-                        float q1[1];
-                        philox_normals<1>(seed, step, sample_offset + b, j, q1);
-                        nz[i][0] = q1[0];
-                        philox_normals<1>(seed, step, sample_offset + b, j + 1, q1);
-                        nz[i][1] = q1[0];
-                    }
-                }
+            for (int i = 0; i < S; ++i) {
+                const int64_t j = pt.xo + (int64_t)i * op.width;  // flat element index of the row
+                sr_row_noise<PW, XI_IN>(xi, seed, step, sample_offset, b, op.n, j, nz[i]);
             }
         }
         // every product and sum of the step rounds on its own (no contraction): the bits are those
@@ -561,19 +549,22 @@ int64_t sr_partials(const sp_op* op) {
     return (patches + sr_tile(op) - 1) / sr_tile(op);
 }
 
-// KERNEL<S, PW> for the operator's factor and path (W % 4 != 0 implies factor 2)
-#define SR_LAUNCH(KIND, WORK, KERNEL, ...)                                                      \
-    do {                                                                                        \
-        const dim3 grid_(static_cast<unsigned>(sr_partials(op)), static_cast<unsigned>(batch)); \
-        if (!sr_vec(op))                                                                        \
-            launch_w(KIND, WORK, KERNEL<2, 2>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
-        else if (op->factor == 2)                                                               \
-            launch_w(KIND, WORK, KERNEL<2, 4>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
-        else if (op->factor == 4)                                                               \
-            launch_w(KIND, WORK, KERNEL<4, 4>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
-        else                                                                                    \
-            launch_w(KIND, WORK, KERNEL<8, 4>, grid_, dim3(kBlock), s, __VA_ARGS__);            \
-    } while (0)
+// f(S, PW) for the operator's factor and path (W % 4 != 0 implies factor 2)
+template <typename F>
+static void sr_select(const sp_op* op, F&& f) {
+    if (!sr_vec(op)) f(int_c<2>{}, int_c<2>{});
+    else if (op->factor == 2) f(int_c<2>{}, int_c<4>{});
+    else if (op->factor == 4) f(int_c<4>{}, int_c<4>{});
+    else f(int_c<8>{}, int_c<4>{});
+}
+
+static dim3 sr_grid(const sp_op* op, int64_t batch) { return sample_grid(sr_partials(op), batch); }
+
+// KERNEL<S, PW> over the operator's tiles (a template's name cannot be passed to a function)
+#define SR_LAUNCH(KIND, WORK, KERNEL, ...)                                                    \
+    sr_select(op, [&](auto S, auto PW) {                                                      \
+        launch_w(KIND, WORK, KERNEL<S(), PW()>, sr_grid(op, batch), dim3(kBlock), s, __VA_ARGS__); \
+    })
 
 int sr_apply(const sp_op* op, const float* x, float* y, int64_t batch, hipStream_t s) {
     SR_LAUNCH(0, 0.0, k_sr_apply, *op, x, y);
@@ -617,48 +608,29 @@ int sr_pixel_opt(const sp_op* op, float* x, float* exp_avg, float* exp_avg_sq, c
 }
 
 // one launch over the blocks, alone (p.eps null) or inside the DiffPIR step (xi read or drawn)
-template <bool STEP, bool XI_IN>
-static void sr_prox_launch(const sp_op* op, const prox_args& p, hipStream_t s) {
-    const int64_t batch = p.batch;
-#define SR_PROX(S, PW) k_sr_prox<S, PW, STEP, XI_IN>
-    const dim3 grid_(static_cast<unsigned>(sr_partials(op)), static_cast<unsigned>(batch));
-#define SR_PROX_GO(S, PW)                                                                      \
-    launch(0, SR_PROX(S, PW), grid_, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, p.step, \
-           p.sample_offset, p.y_div, p.c, p.out)
-    if (!sr_vec(op)) SR_PROX_GO(2, 2);
-    else if (op->factor == 2) SR_PROX_GO(2, 4);
-    else if (op->factor == 4) SR_PROX_GO(4, 4);
-    else SR_PROX_GO(8, 4);
-#undef SR_PROX_GO
-#undef SR_PROX
-}
-
 int sr_prox(const sp_op* op, const prox_args& p, hipStream_t s) {
-    if (!p.eps) sr_prox_launch<false, false>(op, p, s);
-    else if (p.xi) sr_prox_launch<true, true>(op, p, s);
-    else sr_prox_launch<true, false>(op, p, s);
+    sr_select(op, [&](auto S, auto PW) {
+        select_bool(p.eps, [&](auto step) {
+            select_bool(p.xi, [&](auto xin) {  // the prox form has no noise: one kernel
+                launch(0, k_sr_prox<S(), PW(), step(), step() && xin()>, sr_grid(op, p.batch),
+                       dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, p.step, p.sample_offset,
+                       p.y_div, p.c, p.out);
+            });
+        });
+    });
     return check_launch(p.eps ? "sp_diffpir_step_ws" : "sp_op_prox_ws");
 }
 
 // the DDRM step: one launch over the blocks, xi read or drawn
-template <bool XI_IN>
-static void sr_ddrm_launch(const sp_op* op, const ddrm_args& p, hipStream_t s) {
-    const dim3 grid_(static_cast<unsigned>(sr_partials(op)), static_cast<unsigned>(p.batch));
+int sr_ddrm(const sp_op* op, const ddrm_args& p, hipStream_t s) {
     const float g = 1.f / static_cast<float>(op->factor * op->factor);  // the squared singular value
     const ddrm_f fo = ddrm_class_coefs(p.c, g, true), fu = ddrm_class_coefs(p.c, g, false);
-#define SR_DDRM_GO(S, PW)                                                                         \
-    launch(0, k_sr_ddrm<S, PW, XI_IN>, grid_, dim3(kBlock), s, *op, p.x, p.eps, p.y, p.xi, p.seed, \
-           p.step, p.sample_offset, p.y_div, p.c, fo, fu, p.out)
-    if (!sr_vec(op)) SR_DDRM_GO(2, 2);
-    else if (op->factor == 2) SR_DDRM_GO(2, 4);
-    else if (op->factor == 4) SR_DDRM_GO(4, 4);
-    else SR_DDRM_GO(8, 4);
-#undef SR_DDRM_GO
-}
-
-int sr_ddrm(const sp_op* op, const ddrm_args& p, hipStream_t s) {
-    if (p.xi) sr_ddrm_launch<true>(op, p, s);
-    else sr_ddrm_launch<false>(op, p, s);
+    sr_select(op, [&](auto S, auto PW) {
+        select_bool(p.xi, [&](auto xin) {
+            launch(0, k_sr_ddrm<S(), PW(), xin()>, sr_grid(op, p.batch), dim3(kBlock), s, *op, p.x,
+                   p.eps, p.y, p.xi, p.seed, p.step, p.sample_offset, p.y_div, p.c, fo, fu, p.out);
+        });
+    });
     return check_launch("sp_ddrm_step_ws");
 }
 

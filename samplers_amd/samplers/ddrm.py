@@ -43,15 +43,13 @@ import torch
 from torch import Tensor
 
 from samplers_amd import _hip
-from samplers_amd.dtypes import Shape
 from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod, host_timesteps
+from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod
 from samplers_amd.noise import GaussianNoise
 from samplers_amd.operators.linear import SVDOperator
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.dps import (FusedDPSStep, KernelTimer, NoiseFn, draw_seed,
-                                       initial_sample)
-from samplers_amd.samplers.utils.batch_view import BatchView
+from samplers_amd.samplers.dps import FusedStep, KernelTimer, NoiseFn
+from samplers_amd.samplers.loop import run_sampler
 from samplers_amd.samplers.utils.bridge_kernels import (DDRMCoefficients, ddrm_coefficients,
                                                         x0_coefficients)
 
@@ -65,7 +63,7 @@ SUPPORTED = ("IdentityOperator, InpaintingOperator (and subclasses), SuperResolu
 def ddrm_descriptor(operator) -> "_hip.SpOp | None":
     """The operator's HIP descriptor if the library has a DDRM step for its kind
     (``sp_ddrm_workspace`` is the probe; it answers on the host), else None."""
-    desc = getattr(operator, "hip_descriptor", lambda: None)()
+    desc = _hip.descriptor_of(operator)
     if desc is None or int(_hip.load_library().sp_ddrm_workspace(desc, 1)) < 0:
         return None
     return desc
@@ -114,7 +112,7 @@ def _check_unit(name: str, v: float) -> float:
     return float(v)
 
 
-class FusedDDRMStep:
+class FusedDDRMStep(FusedStep):
     """One DDRM iteration over a flat batch: the prior's forward under ``no_grad`` and
     ``sp_ddrm_step_ws`` (or ``ddrm_step_svd`` for an ``SVDOperator`` without a descriptor: plain
     torch on the tensors' device).  Owns what is fixed across the steps: ``q`` (the periodic
@@ -136,35 +134,18 @@ class FusedDDRMStep:
         else:
             raise ValueError(f"DDRM needs GaussianNoise (its sigma is sigma_y) or an explicit "
                              f"noise_std, got {type(noise).__name__}")
-        self.network, self.operator = network, op
-        self.y_div = int(y_div)
-        self.micro_batch, self.timer = micro_batch, timer
-        self._work: Tensor | None = None
-        self.q = None
+        super().__init__(network, op, y_div, micro_batch, timer)
         self.desc = ddrm_descriptor(op)
         self.fused = self.desc is not None
         if not self.fused:
-            has_desc = getattr(op, "hip_descriptor", lambda: None)() is not None
-            if not isinstance(op, SVDOperator) or has_desc:
+            if not isinstance(op, SVDOperator) or _hip.descriptor_of(op) is not None:
                 raise NotImplementedError(
                     f"{type(op).__name__} has no DDRM step: DDRMSampler supports {SUPPORTED}")
             self.y = observation_rows
             return
-        _hip.require_cuda(observation_rows, "DDRMSampler")
-        if observation_rows.dtype != torch.float32:
-            raise TypeError("the HIP path computes in fp32; cast the observation to float32")
-        self.lib = lib = _hip.load_library()
-        self.y = observation_rows.contiguous()
-        rows = self.y.shape[0]
-        if int(lib.sp_ddrm_workspace(self.desc, 1)) > 0:  # the periodic kind: Q = P FFT2(y) / (H W)
-            floats = int(lib.sp_op_workspace(self.desc, rows))
-            if floats <= 0:
-                raise _hip.HipLibraryError(f"sp_op_workspace rejected the descriptor ({floats})")
-            self.q = torch.empty((rows, floats // rows), device=self.y.device, dtype=torch.float32)
-            _hip.check(lib.sp_pgdm_prepare(self.desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
-                                           _hip.stream_of(self.y)), "sp_pgdm_prepare")
-
-    _chunks = FusedDPSStep._chunks
+        self._bind_rows(observation_rows, "DDRMSampler")
+        if int(self.lib.sp_ddrm_workspace(self.desc, 1)) > 0:  # the periodic kind: Q = P FFT2(y) / (H W)
+            self._prepare_q("sp_op_workspace", "sp_pgdm_prepare")
 
     def coefficients(self, t: int, t_prev: int) -> DDRMCoefficients:
         return ddrm_coefficients(host_alphas_cumprod(self.network), t, t_prev, self.sigma, self.eta,
@@ -178,9 +159,7 @@ class FusedDDRMStep:
         floats = int(self.lib.sp_ddrm_workspace(self.desc, batch))
         if floats < 0:
             raise _hip.HipLibraryError(f"sp_ddrm_workspace rejected the descriptor ({floats})")
-        if self._work is None or self._work.numel() < floats or self._work.device != like.device:
-            self._work = torch.empty(floats, device=like.device, dtype=torch.float32)
-        return self._work
+        return self._kept_work(floats, like)
 
     def _noise(self, xc: Tensor, seed: int, step: int, sample_offset: int) -> Tensor:
         """The Philox plane of the fused path, for the torch path on a device tensor."""
@@ -203,31 +182,28 @@ class FusedDDRMStep:
                 eps = self.network.forward(xc, t)
             eps = eps.contiguous()
             xic = None if xi is None else xi[b0:b1].contiguous()
-            span = self.timer.span("ddrm_step", bc) if self.timer else None
-            if span:
-                span.__enter__()
-            if self.fused:
-                coefs = _hip.SpDdrmCoefs(c.a, c.k, c.a_prev, c.sig_prev, c.sig_y, c.eta, c.eta_b, c.c1)
-                _hip.check(self.lib.sp_ddrm_step_ws(
-                    self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
-                    _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed, step,
-                    sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
-                    _hip.ptr(self.workspace(bc, xc)), _hip.stream_of(x)), "sp_ddrm_step_ws")
-            else:
-                if xic is None:
-                    xic = self._noise(xc, seed, step, sample_offset + b0)
-                with torch.no_grad():
-                    yc = self.y[row:row + -(-bc // self.y_div)].to(device=xc.device)
-                    xc.copy_(ddrm_step_svd(self.operator, xc, eps, yc, xic.to(xc.dtype), c))
-            if span:
-                span.__exit__(None, None, None)
+            with self._timed("ddrm_step", bc):
+                if self.fused:
+                    coefs = _hip.SpDdrmCoefs(c.a, c.k, c.a_prev, c.sig_prev, c.sig_y, c.eta, c.eta_b,
+                                             c.c1)
+                    _hip.check(self.lib.sp_ddrm_step_ws(
+                        self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
+                        _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed,
+                        step, sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
+                        _hip.ptr(self.workspace(bc, xc)), _hip.stream_of(x)), "sp_ddrm_step_ws")
+                else:
+                    if xic is None:
+                        xic = self._noise(xc, seed, step, sample_offset + b0)
+                    with torch.no_grad():
+                        yc = self.y[row:row + -(-bc // self.y_div)].to(device=xc.device)
+                        xc.copy_(ddrm_step_svd(self.operator, xc, eps, yc, xic.to(xc.dtype), c))
         return x
 
     def predict_x0(self, x: Tensor, t: int) -> Tensor:
         """Final ``predict_x0``: the prior's forward and ``(x − k·eps)/a`` (``sp_predict_x0`` on
         the fused path)."""
         if self.fused:
-            return FusedDPSStep.predict_x0(self, x, t)
+            return super().predict_x0(x, t)
         a, k = x0_coefficients(host_alphas_cumprod(self.network), t)
         out = torch.empty_like(x)
         for b0, b1 in self._chunks(x.shape[0]):
@@ -265,39 +241,14 @@ class DDRMSampler(PosteriorSampler, Generic[Condition_co]):
         step object of the last call stays on the sampler as ``last_step``."""
         if args or kwargs:
             print(f"Warning: Unused args={args}, kwargs={kwargs} in DDRMSampler")
-        operator = inverse_problem.operator
-        x_shape: Shape = operator.x_shape
-        batch_shape: Shape = inverse_problem.batch_shape
-        view = BatchView(batch_shape=batch_shape, num_samples=num_reconstructions, data_shape=x_shape)
-        net = self._network
-        net.set_sampling_parameters(num_sampling_steps=num_sampling_steps,
-                                    num_reconstructions=num_reconstructions,
-                                    batch_size=view.batch_size)
-        net.set_condition(condition=condition)
-        try:
-            obs = inverse_problem.observation
-            y_rows = obs.reshape(max(view.batch_size, 1), *operator.y_shape).to(torch.float32)
-            step = FusedDDRMStep(net, inverse_problem, y_rows, num_reconstructions, eta=eta,
-                                 eta_b=eta_b, noise_std=noise_std, micro_batch=micro_batch,
-                                 timer=timer)
-            self.last_step = step
-            if seed is None and noise_fn is None and rng == "philox":
-                seed = draw_seed()
-            seed = int(seed or 0)
-            x = initial_sample(view.flat_shape, net.device, rng=rng, seed=seed,
-                               sample_offset=sample_offset, noise_fn=noise_fn)
-            ts = host_timesteps(net)
-            for i in range(len(ts) - 1, 1, -1):
-                xi = None
-                if noise_fn is not None:
-                    xi = noise_fn("step", i, tuple(x.shape)).to(device=x.device, dtype=torch.float32)
-                elif rng == "torch":
-                    xi = torch.randn_like(x)
-                step(x, i, ts[i], ts[i - 1], xi=xi, seed=seed, sample_offset=sample_offset)
-            x0_final = view.unflatten(step.predict_x0(x, ts[1]))
-            if num_reconstructions == 1 and not keep_reconstruction_dim:
-                x0_final = x0_final.squeeze(len(batch_shape))
-            return self._as_output(x0_final)
-        finally:
-            net.clear_condition()
-            net.clear_sampling_parameters()
+
+        def make_step(net, y_rows):
+            self.last_step = FusedDDRMStep(net, inverse_problem, y_rows, num_reconstructions,
+                                           eta=eta, eta_b=eta_b, noise_std=noise_std,
+                                           micro_batch=micro_batch, timer=timer)
+            return self.last_step
+
+        return run_sampler(self, inverse_problem, make_step, num_sampling_steps=num_sampling_steps,
+                           num_reconstructions=num_reconstructions, condition=condition, rng=rng,
+                           seed=seed, noise_fn=noise_fn, sample_offset=sample_offset,
+                           keep_reconstruction_dim=keep_reconstruction_dim)

@@ -32,14 +32,12 @@ import torch
 from torch import Tensor
 
 from samplers_amd import _hip
-from samplers_amd.dtypes import Shape
 from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod, host_timesteps
+from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod
 from samplers_amd.noise import GaussianNoise
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.dps import (FusedDPSStep, KernelTimer, NoiseFn, draw_seed,
-                                       initial_sample)
-from samplers_amd.samplers.utils.batch_view import BatchView
+from samplers_amd.samplers.dps import FusedStep, KernelTimer, NoiseFn
+from samplers_amd.samplers.loop import run_sampler
 from samplers_amd.samplers.utils.bridge_kernels import diffpir_coefficients
 
 Condition_co = TypeVar("Condition_co", covariant=True)
@@ -49,7 +47,7 @@ def prox_descriptor(operator) -> "_hip.SpOp":
     """The operator's HIP descriptor if the library has a proximal map for its kind
     (``sp_prox_workspace`` is the probe; it answers on the host), else ``NotImplementedError``
     naming the operator."""
-    desc = getattr(operator, "hip_descriptor", lambda: None)()
+    desc = _hip.descriptor_of(operator)
     if desc is None or int(_hip.load_library().sp_prox_workspace(desc, 1)) < 0:
         raise NotImplementedError(
             f"{type(operator).__name__} has no closed-form proximal map (apply_prox): DiffPIR "
@@ -65,7 +63,7 @@ PROX_MODES = ("closed_form", "cg", "auto")
 def cg_descriptor(operator) -> "_hip.SpOp":
     """The operator's HIP descriptor if ``sp_diffpir_step_cg_ws`` serves its kind (every linear
     kind; ``sp_prox_cg_workspace`` is the probe), else ``NotImplementedError`` naming it."""
-    desc = getattr(operator, "hip_descriptor", lambda: None)()
+    desc = _hip.descriptor_of(operator)
     if desc is None or int(_hip.load_library().sp_prox_cg_workspace(desc, 1, 1)) < 0:
         raise NotImplementedError(
             f"{type(operator).__name__} has no linear HIP maps for the conjugate-gradient "
@@ -73,7 +71,7 @@ def cg_descriptor(operator) -> "_hip.SpOp":
     return desc
 
 
-class FusedDiffPIRStep:
+class FusedDiffPIRStep(FusedStep):
     """One DiffPIR iteration over a flat batch: the prior's forward under ``no_grad`` and
     ``sp_diffpir_step_ws``.  Owns what is fixed across the steps: ``q`` (the prepared observation
     of the kinds that transform it, once per call), the workspace of a chunk and the micro-batch
@@ -107,33 +105,14 @@ class FusedDiffPIRStep:
         self.cg_iterations, self.cg_tol = int(cg_iterations), float(cg_tol)
         self.cg = prox == "cg"
         if prox == "auto":  # the closed form where sp_prox_workspace has one
-            desc = getattr(op, "hip_descriptor", lambda: None)()
+            desc = _hip.descriptor_of(op)
             self.cg = desc is None or int(_hip.load_library().sp_prox_workspace(desc, 1)) < 0
         self.desc = cg_descriptor(op) if self.cg else prox_descriptor(op)
         self.iterations: Tensor | None = None
-        _hip.require_cuda(observation_rows, "DiffPIRSampler")
-        if observation_rows.dtype != torch.float32:
-            raise TypeError("the HIP path computes in fp32; cast the observation to float32")
-        self.lib = lib = _hip.load_library()
-        self.network, self.operator = network, op
-        self.y = observation_rows.contiguous()
-        self.y_div = int(y_div)
-        self.micro_batch, self.timer = micro_batch, timer
-        self._work: Tensor | None = None
-        rows = self.y.shape[0]
-        self.q = None
-        if self.cg:  # nothing to prepare: the maps read y itself
-            return
-        qsize = int(lib.sp_prox_prepare_size(self.desc, rows))
-        if qsize < 0:
-            raise _hip.HipLibraryError(f"sp_prox_prepare_size rejected the descriptor ({qsize})")
-        if qsize:
-            self.q = torch.empty((rows, qsize // rows), device=self.y.device, dtype=torch.float32)
-            _hip.check(lib.sp_prox_prepare(self.desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
-                                           _hip.stream_of(self.y)), "sp_prox_prepare")
-
-    _chunks = FusedDPSStep._chunks
-    predict_x0 = FusedDPSStep.predict_x0
+        super().__init__(network, op, y_div, micro_batch, timer)
+        self._bind_rows(observation_rows, "DiffPIRSampler")
+        if not self.cg:  # conjugate gradients prepare nothing: the maps read y itself
+            self._prepare_q("sp_prox_prepare_size", "sp_prox_prepare", optional=True)
 
     def coefficients(self, t: int, t_prev: int) -> _hip.SpProxCoefs:
         c = diffpir_coefficients(host_alphas_cumprod(self.network), t, t_prev, self.sigma,
@@ -149,9 +128,7 @@ class FusedDiffPIRStep:
                      else self.lib.sp_prox_workspace(self.desc, batch))
         if floats < 0:
             raise _hip.HipLibraryError(f"sp_prox_workspace rejected the descriptor ({floats})")
-        if self._work is None or self._work.numel() < floats or self._work.device != like.device:
-            self._work = torch.empty(floats, device=like.device, dtype=torch.float32)
-        return self._work
+        return self._kept_work(floats, like)
 
     def __call__(self, x: Tensor, step: int, t: int, t_prev: int, *, xi: Tensor | None = None,
                  seed: int = 0, sample_offset: int = 0) -> Tensor:
@@ -165,23 +142,19 @@ class FusedDiffPIRStep:
                 eps = self.network.forward(xc, t)
             eps = eps.contiguous()
             xic = None if xi is None else xi[b0:b1].contiguous()
-            span = self.timer.span("diffpir_step", bc) if self.timer else None
-            if span:
-                span.__enter__()
-            if self.cg:
-                _hip.check(self.lib.sp_diffpir_step_cg_ws(
-                    self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]), _hip.ptr(xic),
-                    seed, step, sample_offset + b0, bc, self.y_div, coefs, self.cg_iterations,
-                    self.cg_tol, _hip.ptr(xc), _hip.ptr(iters[b0:b1]),
-                    _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_cg_ws")
-            else:
-                _hip.check(self.lib.sp_diffpir_step_ws(
-                    self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
-                    _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed, step,
-                    sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
-                    _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_ws")
-            if span:
-                span.__exit__(None, None, None)
+            with self._timed("diffpir_step", bc):
+                if self.cg:
+                    _hip.check(self.lib.sp_diffpir_step_cg_ws(
+                        self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
+                        _hip.ptr(xic), seed, step, sample_offset + b0, bc, self.y_div, coefs,
+                        self.cg_iterations, self.cg_tol, _hip.ptr(xc), _hip.ptr(iters[b0:b1]),
+                        _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_cg_ws")
+                else:
+                    _hip.check(self.lib.sp_diffpir_step_ws(
+                        self.desc, _hip.ptr(xc), _hip.ptr(eps), _hip.ptr(self.y[row:]),
+                        _hip.ptr(self.q[row:]) if self.q is not None else None, _hip.ptr(xic), seed,
+                        step, sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
+                        _hip.ptr(self.workspace(bc, xc)), stream), "sp_diffpir_step_ws")
         if iters is not None:  # appended on the device; nothing here waits for it
             self.iterations = (iters[None] if self.iterations is None
                                else torch.cat([self.iterations, iters[None]]))
@@ -223,41 +196,15 @@ class DiffPIRSampler(PosteriorSampler, Generic[Condition_co]):
         sampler as ``last_step`` (its ``iterations``: the conjugate-gradient counts per step)."""
         if args or kwargs:
             print(f"Warning: Unused args={args}, kwargs={kwargs} in DiffPIRSampler")
-        operator = inverse_problem.operator
-        x_shape: Shape = operator.x_shape
-        batch_shape: Shape = inverse_problem.batch_shape
-        view = BatchView(batch_shape=batch_shape, num_samples=num_reconstructions, data_shape=x_shape)
-        net = self._network
-        net.set_sampling_parameters(num_sampling_steps=num_sampling_steps,
-                                    num_reconstructions=num_reconstructions,
-                                    batch_size=view.batch_size)
-        net.set_condition(condition=condition)
-        try:
-            obs = inverse_problem.observation
-            y_rows = obs.reshape(max(view.batch_size, 1), *operator.y_shape).to(torch.float32)
-            step = FusedDiffPIRStep(net, inverse_problem, y_rows, num_reconstructions,
-                                    guidance_weight=guidance_weight, zeta=zeta,
-                                    min_noise_std=min_noise_std, micro_batch=micro_batch,
-                                    timer=timer, prox=prox, cg_iterations=cg_iterations,
-                                    cg_tol=cg_tol)
-            self.last_step = step
-            if seed is None and noise_fn is None and rng == "philox":
-                seed = draw_seed()
-            seed = int(seed or 0)
-            x = initial_sample(view.flat_shape, net.device, rng=rng, seed=seed,
-                               sample_offset=sample_offset, noise_fn=noise_fn)
-            ts = host_timesteps(net)
-            for i in range(len(ts) - 1, 1, -1):
-                xi = None
-                if noise_fn is not None:
-                    xi = noise_fn("step", i, tuple(x.shape)).to(device=x.device, dtype=torch.float32)
-                elif rng == "torch":
-                    xi = torch.randn_like(x)
-                step(x, i, ts[i], ts[i - 1], xi=xi, seed=seed, sample_offset=sample_offset)
-            x0_final = view.unflatten(step.predict_x0(x, ts[1]))
-            if num_reconstructions == 1 and not keep_reconstruction_dim:
-                x0_final = x0_final.squeeze(len(batch_shape))
-            return self._as_output(x0_final)
-        finally:
-            net.clear_condition()
-            net.clear_sampling_parameters()
+
+        def make_step(net, y_rows):
+            self.last_step = FusedDiffPIRStep(
+                net, inverse_problem, y_rows, num_reconstructions, guidance_weight=guidance_weight,
+                zeta=zeta, min_noise_std=min_noise_std, micro_batch=micro_batch, timer=timer,
+                prox=prox, cg_iterations=cg_iterations, cg_tol=cg_tol)
+            return self.last_step
+
+        return run_sampler(self, inverse_problem, make_step, num_sampling_steps=num_sampling_steps,
+                           num_reconstructions=num_reconstructions, condition=condition, rng=rng,
+                           seed=seed, noise_fn=noise_fn, sample_offset=sample_offset,
+                           keep_reconstruction_dim=keep_reconstruction_dim)

@@ -27,6 +27,7 @@ Noise (``rng=``):
 
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Generic, TypeVar
 
 import numpy as np
@@ -34,21 +35,14 @@ import torch
 from torch import Tensor
 
 from samplers_amd import _hip
-from samplers_amd.dtypes import Shape
 from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod, host_timesteps
+from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.utils.batch_view import BatchView
+from samplers_amd.samplers.loop import (NoiseFn, draw_seed, initial_sample,  # noqa: F401
+                                        run_sampler)
 from samplers_amd.samplers.utils.bridge_kernels import bridge_coefficients, x0_coefficients
 
 Condition_co = TypeVar("Condition_co", covariant=True)
-
-NoiseFn = Callable[[str, int, tuple], Tensor]
-
-
-def draw_seed() -> int:
-    """A 63-bit seed from torch's default CPU generator (reproducible under manual_seed)."""
-    return int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
 
 
 class KernelTimer:
@@ -113,19 +107,82 @@ class KernelTimer:
         self._lib.sp_timing_enable(0)
 
 
-class FusedDPSStep:
-    """One guided DPS iteration (``dps.py:91-122``) over a flat batch, on HIP.
+class FusedStep:
+    """What the fused steps of the samplers share: the observation rows on the device, ``q`` (the
+    rows as a kind's launches read them, prepared once per call: y is fixed across the steps),
+    the micro-batch chunks, a work buffer kept between steps, the bracket of a launch for
+    ``KernelTimer`` and the final ``predict_x0``.
 
     ``observation_rows``: ``(num_rows, *y_shape)`` fp32 device tensor; sample b
     uses row ``b // y_div`` (``y_div`` = reconstructions per observation).
     """
+
+    def __init__(self, network: EpsilonNetwork, operator, y_div: int, micro_batch: int | None,
+                 timer: KernelTimer | None) -> None:
+        self.network, self.operator = network, operator
+        self.y_div = int(y_div)
+        self.micro_batch, self.timer = micro_batch, timer
+        self.q: Tensor | None = None
+        self._work: Tensor | None = None
+
+    def _bind_rows(self, observation_rows: Tensor, sampler: str) -> None:
+        _hip.require_cuda(observation_rows, sampler)
+        if observation_rows.dtype != torch.float32:
+            raise TypeError("the HIP path computes in fp32; cast the observation to float32")
+        self.lib = _hip.load_library()
+        self.y = observation_rows.contiguous()
+
+    def _prepare_q(self, size: str, prepare: str, *, optional: bool = False) -> None:
+        """``q`` of ``size(desc, rows)`` floats, filled by ``prepare`` (both entry points by name);
+        an ``optional`` one stays None where the kind has nothing to prepare."""
+        rows = self.y.shape[0]
+        floats = int(getattr(self.lib, size)(self.desc, rows))
+        if floats < 0 or not (floats or optional):
+            raise _hip.HipLibraryError(f"{size} rejected the descriptor ({floats})")
+        if floats:
+            self.q = torch.empty((rows, floats // rows), device=self.y.device, dtype=torch.float32)
+            _hip.check(getattr(self.lib, prepare)(self.desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
+                                                  _hip.stream_of(self.y)), prepare)
+
+    def _chunks(self, batch: int):
+        mb = self.micro_batch or batch
+        mb = max(self.y_div, (mb // self.y_div) * self.y_div)  # chunks never split an observation
+        for b0 in range(0, batch, mb):
+            yield b0, min(batch, b0 + mb)
+
+    def _kept_work(self, floats: int, like: Tensor) -> Tensor:
+        """At least ``floats`` floats on ``like``'s device, kept between steps (grow-only)."""
+        if self._work is None or self._work.numel() < floats or self._work.device != like.device:
+            self._work = torch.empty(floats, device=like.device, dtype=torch.float32)
+        return self._work
+
+    def _timed(self, name: str, batch: int):
+        """Brackets one launch for the kernel timer, if there is one."""
+        return self.timer.span(name, batch) if self.timer else contextlib.nullcontext()
+
+    def predict_x0(self, x: Tensor, t: int) -> Tensor:
+        """Final ``predict_x0`` (``dps.py:125-126``): prior forward + HIP epilogue."""
+        a, k = x0_coefficients(host_alphas_cumprod(self.network), t)
+        out = torch.empty_like(x)
+        for b0, b1 in self._chunks(x.shape[0]):
+            with torch.no_grad():
+                eps = self.network.forward(x[b0:b1], t).contiguous()
+            _hip.check(self.lib.sp_predict_x0(_hip.ptr(x[b0:b1]), _hip.ptr(eps), eps.numel(), a, k,
+                                              _hip.ptr(out[b0:b1]), _hip.stream_of(x)),
+                       "sp_predict_x0")
+        return out
+
+
+class FusedDPSStep(FusedStep):
+    """One guided DPS iteration (``dps.py:91-122``) over a flat batch, on HIP.
+    ``observation_rows`` as ``FusedStep``."""
 
     def __init__(self, network: EpsilonNetwork, inverse_problem: InverseProblem,
                  observation_rows: Tensor, y_div: int, *, gamma: float = 1.0, eta: float = 1.0,
                  micro_batch: int | None = None, timer: KernelTimer | None = None,
                  reuse_v: bool = False, mode: str = "dps", guidance_weight: float = 1.0) -> None:
         op = inverse_problem.operator
-        desc = getattr(op, "hip_descriptor", lambda: None)()
+        desc = _hip.descriptor_of(op)
         if desc is None:
             raise NotImplementedError(
                 f"{type(op).__name__} has no native (HIP) implementation; the fused DPS path "
@@ -134,15 +191,9 @@ class FusedDPSStep:
                 "FFTPSFBlurOperator, PeriodicBlurOperator, PeriodicSuperResolutionOperator, "
                 "RadonOperator and PhaseRetrievalOperator"
             )
-        _hip.require_cuda(observation_rows, "DPSSampler")
-        if observation_rows.dtype != torch.float32:
-            raise TypeError("the HIP path computes in fp32; cast the observation to float32")
-        self.lib = _hip.load_library()
-        self.network = network
-        self.operator = op
+        super().__init__(network, op, y_div, micro_batch, timer)
+        self._bind_rows(observation_rows, "DPSSampler")
         self.desc = desc
-        self.y = observation_rows.contiguous()
-        self.y_div = int(y_div)
         self.m = int(desc.m)
         self.n = int(desc.n)
         self.partials = int(self.lib.sp_rsq_partials(desc))
@@ -179,18 +230,9 @@ class FusedDPSStep:
         # re-reading pass 1's v, 42.3 vs 45.2 us at B = 64, 256^2) or re-reads v (reuse_v, and
         # always for the kinds whose pass 2 is the identity-kind kernel over v: the library's trait).
         self.needs_v = bool(self.traits & _hip.SP_TRAIT_UPDATE_READS_V) or bool(reuse_v)
-        self.micro_batch = micro_batch
-        self.timer = timer
         # PGDM through the kind's own pseudo-inverse: Q = P FFT2(y), once (y is fixed across steps)
-        self.q = None
         if mode == "pgdm" and self.pinv:
-            rows = self.y.shape[0]
-            floats = int(self.lib.sp_op_workspace(desc, rows))
-            if floats <= 0:
-                raise _hip.HipLibraryError(f"sp_op_workspace rejected the descriptor ({floats})")
-            self.q = torch.empty((rows, floats // rows), device=self.y.device, dtype=torch.float32)
-            _hip.check(self.lib.sp_pgdm_prepare(desc, _hip.ptr(self.y), rows, _hip.ptr(self.q),
-                                                _hip.stream_of(self.y)), "sp_pgdm_prepare")
+            self._prepare_q("sp_op_workspace", "sp_pgdm_prepare")
 
     def coefficients(self, t: int, t_prev: int, s: int) -> _hip.SpDpsCoefs:
         acp = host_alphas_cumprod(self.network)
@@ -212,12 +254,6 @@ class FusedDPSStep:
             raise _hip.HipLibraryError(f"sp_dps_workspace rejected the descriptor ({floats})")
         return torch.empty(floats, device=like.device, dtype=torch.float32) if floats else None
 
-    def _chunks(self, batch: int):
-        mb = self.micro_batch or batch
-        mb = max(self.y_div, (mb // self.y_div) * self.y_div)  # chunks never split an observation
-        for b0 in range(0, batch, mb):
-            yield b0, min(batch, b0 + mb)
-
     def __call__(self, x: Tensor, step: int, t: int, t_prev: int, s: int, *,
                  xi: Tensor | None = None, seed: int = 0, sample_offset: int = 0) -> Tensor:
         """Advance ``x`` (flat ``(B, *x_shape)``, contiguous fp32) one step, in place."""
@@ -237,51 +273,31 @@ class FusedDPSStep:
                 eps_c = eps_c.contiguous()
             v = torch.empty_like(xc)
             part = torch.empty((bc, self.partials), device=x.device, dtype=torch.float32)
-            span = self.timer.span("dps_residual", bc) if self.timer else None
-            if span:
-                span.__enter__()
-            work = self.workspace(bc, xc)
-            if self.q is not None:
-                _hip.check(lib.sp_pgdm_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c),
-                                                   _hip.ptr(self.q[b0 // self.y_div:]), bc,
-                                                   self.y_div, coefs, _hip.ptr(v), _hip.ptr(work),
-                                                   stream), "sp_pgdm_residual_ws")
-            else:
-                _hip.check(lib.sp_dps_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc),
-                                                  bc, self.y_div, coefs, _hip.ptr(v), _hip.ptr(part),
-                                                  _hip.ptr(work), stream),
-                           "sp_dps_residual_ws")
-            if span:
-                span.__exit__(None, None, None)
+            with self._timed("dps_residual", bc):
+                work = self.workspace(bc, xc)
+                if self.q is not None:
+                    _hip.check(lib.sp_pgdm_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c),
+                                                       _hip.ptr(self.q[b0 // self.y_div:]), bc,
+                                                       self.y_div, coefs, _hip.ptr(v), _hip.ptr(work),
+                                                       stream), "sp_pgdm_residual_ws")
+                else:
+                    _hip.check(lib.sp_dps_residual_ws(desc, _hip.ptr(xc), _hip.ptr(eps_c),
+                                                      _hip.ptr(yc), bc, self.y_div, coefs, _hip.ptr(v),
+                                                      _hip.ptr(part), _hip.ptr(work), stream),
+                               "sp_dps_residual_ws")
             (w,) = torch.autograd.grad(eps, xr, grad_outputs=v.view_as(eps))
             del eps, xr
             w = w.contiguous()
             xic = None if xi is None else xi[b0:b1].contiguous()
-            span = self.timer.span("dps_update", bc) if self.timer else None
-            if span:
-                span.__enter__()
-            _hip.check(lib.sp_dps_update(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc),
-                                         _hip.ptr(v) if self.needs_v else None, _hip.ptr(w),
-                                         _hip.ptr(part) if self.mode == "dps" else None,
-                                         _hip.ptr(xic), seed, step,
-                                         sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
-                                         stream),
-                       "sp_dps_update")
-            if span:
-                span.__exit__(None, None, None)
+            with self._timed("dps_update", bc):
+                _hip.check(lib.sp_dps_update(desc, _hip.ptr(xc), _hip.ptr(eps_c), _hip.ptr(yc),
+                                             _hip.ptr(v) if self.needs_v else None, _hip.ptr(w),
+                                             _hip.ptr(part) if self.mode == "dps" else None,
+                                             _hip.ptr(xic), seed, step,
+                                             sample_offset + b0, bc, self.y_div, coefs, _hip.ptr(xc),
+                                             stream),
+                           "sp_dps_update")
         return x
-
-    def predict_x0(self, x: Tensor, t: int) -> Tensor:
-        """Final ``predict_x0`` (``dps.py:125-126``): prior forward + HIP epilogue."""
-        a, k = x0_coefficients(host_alphas_cumprod(self.network), t)
-        out = torch.empty_like(x)
-        for b0, b1 in self._chunks(x.shape[0]):
-            with torch.no_grad():
-                eps = self.network.forward(x[b0:b1], t).contiguous()
-            _hip.check(self.lib.sp_predict_x0(_hip.ptr(x[b0:b1]), _hip.ptr(eps), eps.numel(), a, k,
-                                              _hip.ptr(out[b0:b1]), _hip.stream_of(x)),
-                       "sp_predict_x0")
-        return out
 
 
 class GenericDPSStep(FusedDPSStep):
@@ -382,8 +398,7 @@ class GenericDPSStep(FusedDPSStep):
 def native_plugins(inverse_problem) -> bool:
     """True when the operator has a HIP descriptor and the noise a constant ∂log p/∂(Ax)
     factor, i.e. the fused passes can replace autograd entirely."""
-    desc_fn = getattr(inverse_problem.operator, "hip_descriptor", None)
-    if desc_fn is None or desc_fn() is None:
+    if _hip.descriptor_of(inverse_problem.operator) is None:
         return False
     gs = getattr(inverse_problem.noise, "grad_scale", None)
     if gs is None:
@@ -396,7 +411,7 @@ def native_plugins(inverse_problem) -> bool:
 def make_dps_step(network, inverse_problem, observation_rows, y_div, **kw):
     """The fused HIP step for native plugins, the generic-plugin step otherwise."""
     mode = kw.get("mode", "dps")
-    native_op = getattr(inverse_problem.operator, "hip_descriptor", lambda: None)() is not None
+    native_op = _hip.descriptor_of(inverse_problem.operator) is not None
     if (mode == "dps" and native_plugins(inverse_problem)) or (mode == "pgdm" and native_op):
         return FusedDPSStep(network, inverse_problem, observation_rows, y_div, **kw)
     return GenericDPSStep(network, inverse_problem, observation_rows, y_div, **kw)
@@ -431,24 +446,6 @@ def graph_auto(step, x: Tensor, guided_steps: int, *, rng: str, noise_fn, callba
             and step.timer is None and rng == "philox" and noise_fn is None and callback is None
             and (not micro_batch or micro_batch >= x.shape[0]) and x.is_cuda
             and 0 < x.shape[0] <= GRAPH_AUTO_MAX_BATCH and guided_steps >= GRAPH_AUTO_MIN_STEPS)
-
-
-def initial_sample(shape: tuple, device: torch.device, *, rng: str, seed: int, sample_offset: int,
-                   noise_fn: NoiseFn | None) -> Tensor:
-    """x_T ~ N(0, I) (``dps.py:83-87``)."""
-    if noise_fn is not None:
-        return noise_fn("init", -1, shape).to(device=device, dtype=torch.float32).contiguous()
-    if rng == "torch":
-        return torch.randn(size=shape, device=device, dtype=torch.float32)
-    if rng != "philox":
-        raise ValueError(f"rng must be 'philox' or 'torch', got {rng!r}")
-    lib = _hip.load_library()
-    x = torch.empty(shape, device=device, dtype=torch.float32)
-    n = x[0].numel() if shape[0] else 0
-    if shape[0]:
-        _hip.check(lib.sp_randn(_hip.ptr(x), shape[0], n, seed, -1, sample_offset,
-                                _hip.stream_of(x)), "sp_randn")
-    return x
 
 
 class DPSSampler(PosteriorSampler, Generic[Condition_co]):
@@ -494,61 +491,32 @@ class DPSSampler(PosteriorSampler, Generic[Condition_co]):
         if args or kwargs:
             print(f"Warning: Unused args={args}, kwargs={kwargs} in DPSSampler")
 
-        x_shape: Shape = inverse_problem.operator.x_shape
-        batch_shape: Shape = inverse_problem.batch_shape
-        view = BatchView(batch_shape=batch_shape, num_samples=num_reconstructions, data_shape=x_shape)
+        def make_step(net, y_rows):
+            return make_dps_step(net, inverse_problem, y_rows, num_reconstructions, gamma=gamma,
+                                 eta=eta, micro_batch=micro_batch, timer=timer)
 
-        net = self._network
-        net.set_sampling_parameters(num_sampling_steps=num_sampling_steps,
-                                    num_reconstructions=num_reconstructions,
-                                    batch_size=view.batch_size)
-        net.set_condition(condition=condition)
-        try:
-            obs = inverse_problem.observation
-            _hip.require_cuda(obs, "DPSSampler")
-            y_rows = obs.reshape(max(view.batch_size, 1), *inverse_problem.operator.y_shape)
-            step = make_dps_step(net, inverse_problem, y_rows.to(torch.float32), num_reconstructions,
-                                 gamma=gamma, eta=eta, micro_batch=micro_batch, timer=timer)
-            if seed is None and noise_fn is None and rng == "philox":
-                seed = draw_seed()
-            seed = int(seed or 0)
+        def advance(step, x, ts, seed, loop):
+            replay = graph
+            if replay is None:
+                replay = graph_auto(step, x, len(ts) - 2, rng=rng, noise_fn=noise_fn,
+                                    callback=callback, micro_batch=micro_batch)
+            self.execution = "graph" if replay else "eager"  # what the last call ran
+            if not replay:
+                return loop(callback)
+            if not isinstance(step, FusedDPSStep) or isinstance(step, GenericDPSStep):
+                raise ValueError("graph=True needs natively implemented plugins")
+            if noise_fn is not None or rng != "philox":
+                raise ValueError("graph=True needs the in-kernel Philox noise (rng='philox')")
+            if callback is not None:
+                raise ValueError("graph=True replays the steps without returning to the host: "
+                                 "no per-iteration callback")
+            from .graph import GraphedStepLoop, schedule_for
 
-            x = initial_sample(view.flat_shape, net.device, rng=rng, seed=seed,
-                               sample_offset=sample_offset, noise_fn=noise_fn)
-            ts = host_timesteps(net)
-            if graph is None:
-                graph = graph_auto(step, x, len(ts) - 2, rng=rng, noise_fn=noise_fn,
-                                   callback=callback, micro_batch=micro_batch)
-            self.execution = "graph" if graph else "eager"  # what the last call ran
-            if graph:
-                if not isinstance(step, FusedDPSStep) or isinstance(step, GenericDPSStep):
-                    raise ValueError("graph=True needs natively implemented plugins")
-                if noise_fn is not None or rng != "philox":
-                    raise ValueError("graph=True needs the in-kernel Philox noise (rng='philox')")
-                if callback is not None:
-                    raise ValueError("graph=True replays the steps without returning to the host: "
-                                     "no per-iteration callback")
-                from .graph import GraphedStepLoop, schedule_for
+            GraphedStepLoop(step, x, schedule_for(ts), seed=seed,
+                            sample_offset=sample_offset).replay()
 
-                GraphedStepLoop(step, x, schedule_for(ts), seed=seed,
-                                sample_offset=sample_offset).replay()
-            else:
-                for i in range(len(ts) - 1, 1, -1):
-                    xi = None
-                    if noise_fn is not None:
-                        xi = noise_fn("step", i, tuple(x.shape)).to(device=x.device,
-                                                                    dtype=torch.float32)
-                    elif rng == "torch":
-                        xi = torch.randn_like(x)
-                    step(x, i, ts[i], ts[i - 1], ts[0], xi=xi, seed=seed,
-                         sample_offset=sample_offset)
-                    if callback is not None:
-                        callback(i, x)
-
-            x0_final = view.unflatten(step.predict_x0(x, ts[1]))
-            if num_reconstructions == 1 and not keep_reconstruction_dim:
-                x0_final = x0_final.squeeze(len(batch_shape))
-            return self._as_output(x0_final)
-        finally:
-            net.clear_condition()
-            net.clear_sampling_parameters()
+        return run_sampler(self, inverse_problem, make_step, num_sampling_steps=num_sampling_steps,
+                           num_reconstructions=num_reconstructions, condition=condition, rng=rng,
+                           seed=seed, noise_fn=noise_fn, sample_offset=sample_offset,
+                           keep_reconstruction_dim=keep_reconstruction_dim, require="DPSSampler",
+                           anchored=True, advance=advance)

@@ -20,13 +20,10 @@ from typing import Generic, TypeVar
 import torch
 from torch import Tensor
 
-from samplers_amd import _hip
-from samplers_amd.dtypes import Shape
 from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.networks.base import host_timesteps
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.dps import KernelTimer, NoiseFn, draw_seed, initial_sample, make_dps_step
-from samplers_amd.samplers.utils.batch_view import BatchView
+from samplers_amd.samplers.dps import KernelTimer, NoiseFn, make_dps_step
+from samplers_amd.samplers.loop import run_sampler
 
 Condition_co = TypeVar("Condition_co", covariant=True)
 
@@ -64,38 +61,14 @@ class PGDMSampler(PosteriorSampler, Generic[Condition_co]):
         if args or kwargs:
             print(f"Warning: Unused args={args}, kwargs={kwargs} in PGDMSampler")
 
-        x_shape: Shape = operator.x_shape
-        batch_shape: Shape = inverse_problem.batch_shape
-        view = BatchView(batch_shape=batch_shape, num_samples=num_reconstructions, data_shape=x_shape)
-        net = self._network
-        net.set_sampling_parameters(num_sampling_steps=num_sampling_steps,
-                                    num_reconstructions=num_reconstructions,
-                                    batch_size=view.batch_size)
-        net.set_condition(condition=condition)
-        try:
-            obs = inverse_problem.observation
-            _hip.require_cuda(obs, "PGDMSampler")
-            y_rows = obs.reshape(max(view.batch_size, 1), *operator.y_shape).to(torch.float32)
-            step = make_dps_step(net, inverse_problem, y_rows, num_reconstructions, eta=eta,
+
+        def make_step(net, y_rows):
+            return make_dps_step(net, inverse_problem, y_rows, num_reconstructions, eta=eta,
                                  micro_batch=micro_batch, timer=timer, mode="pgdm",
                                  guidance_weight=guidance_weight)
-            if seed is None and noise_fn is None and rng == "philox":
-                seed = draw_seed()
-            seed = int(seed or 0)
-            x = initial_sample(view.flat_shape, net.device, rng=rng, seed=seed,
-                               sample_offset=sample_offset, noise_fn=noise_fn)
-            ts = host_timesteps(net)
-            for i in range(len(ts) - 1, 1, -1):
-                xi = None
-                if noise_fn is not None:
-                    xi = noise_fn("step", i, tuple(x.shape)).to(device=x.device, dtype=torch.float32)
-                elif rng == "torch":
-                    xi = torch.randn_like(x)
-                step(x, i, ts[i], ts[i - 1], ts[0], xi=xi, seed=seed, sample_offset=sample_offset)
-            x0_final = view.unflatten(step.predict_x0(x, ts[1]))
-            if num_reconstructions == 1 and not keep_reconstruction_dim:
-                x0_final = x0_final.squeeze(len(batch_shape))
-            return self._as_output(x0_final)
-        finally:
-            net.clear_condition()
-            net.clear_sampling_parameters()
+
+        return run_sampler(self, inverse_problem, make_step, num_sampling_steps=num_sampling_steps,
+                           num_reconstructions=num_reconstructions, condition=condition, rng=rng,
+                           seed=seed, noise_fn=noise_fn, sample_offset=sample_offset,
+                           keep_reconstruction_dim=keep_reconstruction_dim, require="PGDMSampler",
+                           anchored=True)

@@ -34,10 +34,10 @@ from samplers_amd import _hip
 from samplers_amd.distributed import all_reduce_sum_
 from samplers_amd.dtypes import Shape
 from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.networks.base import LatentEpsilonNetwork, host_alphas_cumprod, host_timesteps
+from samplers_amd.networks.base import LatentEpsilonNetwork, host_alphas_cumprod
 from samplers_amd.operators import IdentityOperator
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.dps import NoiseFn, draw_seed, initial_sample
+from samplers_amd.samplers.loop import NoiseFn, run_sampler
 from samplers_amd.samplers.utils.batch_view import BatchView
 from samplers_amd.samplers.utils.bridge_kernels import bridge_coefficients, x0_coefficients
 
@@ -70,7 +70,7 @@ class FusedPSLDStep:
                  observation_rows: Tensor, y_div: int, latent_shape: Shape, *, gamma: float = 1.0,
                  omega: float = 0.1, eta: float = 1.0, group=None) -> None:
         op = inverse_problem.operator
-        desc = getattr(op, "hip_descriptor", lambda: None)()
+        desc = _hip.descriptor_of(op)
         if not getattr(op, "hip_linear", True):  # nonlinear native operator: the generic route,
             desc = None                          # which needs (and fails at) apply_transpose
         _hip.require_cuda(observation_rows, "PSLDSampler")
@@ -253,38 +253,22 @@ class PSLDSampler(PosteriorSampler, Generic[Condition_co]):
     ) -> Tensor:
         x_shape: Shape = inverse_problem.operator.x_shape
         batch_shape: Shape = inverse_problem.batch_shape
-        x_view = BatchView(batch_shape, num_reconstructions, x_shape)
         net: LatentEpsilonNetwork = self._network
         latent_shape: Shape = tuple(net.get_latent_shape(x_shape))
-        z_view = BatchView(batch_shape, num_reconstructions, latent_shape)
 
-        net.set_sampling_parameters(num_sampling_steps=num_sampling_steps,
-                                    num_reconstructions=num_reconstructions,
-                                    batch_size=x_view.batch_size)
-        net.set_condition(condition)
-        try:
-            obs = inverse_problem.observation
-            _hip.require_cuda(obs, "PSLDSampler")
-            y_rows = obs.reshape(max(x_view.batch_size, 1), -1).to(torch.float32)
-            step = FusedPSLDStep(net, inverse_problem, y_rows, num_reconstructions, latent_shape,
+        def make_step(net, y_rows):
+            return FusedPSLDStep(net, inverse_problem, y_rows, num_reconstructions, latent_shape,
                                  gamma=gamma, omega=omega, eta=eta, group=group)
-            if seed is None and noise_fn is None and rng == "philox":
-                seed = draw_seed()
-            seed = int(seed or 0)
-            z = initial_sample(z_view.flat_shape, net.device, rng=rng, seed=seed,
-                               sample_offset=sample_offset, noise_fn=noise_fn)
-            ts = host_timesteps(net)
-            for i in range(len(ts) - 1, 1, -1):
-                xi = None
-                if noise_fn is not None:
-                    xi = noise_fn("step", i, tuple(z.shape)).to(device=z.device, dtype=torch.float32)
-                elif rng == "torch":
-                    xi = torch.randn_like(z)
-                step(z, i, ts[i], ts[i - 1], ts[0], xi=xi, seed=seed, sample_offset=sample_offset)
-            final_z0 = step.predict_x0(z, ts[1])
+
+        def finish(final_z0):
             if decode_output:
+                x_view = BatchView(batch_shape, num_reconstructions, x_shape)
                 return self._as_output(x_view.unflatten(net.decode(final_z0, differentiable=False)))
+            z_view = BatchView(batch_shape, num_reconstructions, latent_shape)
             return self._as_output(z_view.unflatten(final_z0))
-        finally:
-            net.clear_condition()
-            net.clear_sampling_parameters()
+
+        return run_sampler(self, inverse_problem, make_step, num_sampling_steps=num_sampling_steps,
+                           num_reconstructions=num_reconstructions, condition=condition, rng=rng,
+                           seed=seed, noise_fn=noise_fn, sample_offset=sample_offset,
+                           require="PSLDSampler", anchored=True, data_shape=latent_shape,
+                           y_shape=(-1,), finish=finish)

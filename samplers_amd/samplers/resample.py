@@ -208,7 +208,7 @@ def _finish_log(owner) -> None:
 def make_consistency(operator, y_rows: Tensor, y_div: int, group=None) -> _Consistency:
     # no descriptor, or a nonlinear native operator (no sp_op_adjoint): autograd through apply,
     # which for the latter is its HIP forward and HIP VJP
-    if (getattr(operator, "hip_descriptor", lambda: None)() is None
+    if (_hip.descriptor_of(operator) is None
             or not getattr(operator, "hip_linear", True)):
         return _GenericConsistency(operator, y_rows, y_div, group)
     return _Consistency(operator, y_rows, y_div, group)
