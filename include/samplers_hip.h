@@ -101,7 +101,7 @@ enum {
                            1 <= factor <= 1024 bins; taps holds one row per angle
                            (below).  Linear, adjoint = exact transpose (a gather per
                            pixel, no atomics); no pseudo-inverse                */
-    SP_OP_SR_PERIODIC = 10 /* new: periodic blur-and-decimate x factor super-resolution
+    SP_OP_SR_PERIODIC = 10, /* new: periodic blur-and-decimate x factor super-resolution
                            (bicubic, Gaussian blur + decimation), depthwise:
                            y[c][i][j] = sum_{u,v} h[u][v] x[c][(factor*i + u - P) mod H]
                            [(factor*j + v - P) mod W] over radius^2 taps, P = (radius -
@@ -115,6 +115,17 @@ enum {
                            workspace: sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
                            sp_op_pinv_ws = A^+ / A^+T, and the fused PGDM and prox
                            passes as PSF_PERIODIC                                 */
+    SP_OP_SVD_SEPARABLE = 11 /* new: A X = A_H X A_W^T on every channel plane, A_H (Hy x H)
+                           and A_W (Wy x W) any dense matrices (a blur under any boundary
+                           rule, filter-and-decimate super-resolution), given by their
+                           SVDs: A = (U_H (x) U_W) diag(s_H[i] s_W[j]) (V_H (x) V_W)^T.  y is
+                           (channels, radius, factor) = (C, Hy, Wy); 2 <= height, width <=
+                           512, 1 <= Hy <= height, 1 <= Wy <= width, any integers;
+                           m = channels*Hy*Wy; taps holds the six tables (below).  Per-plane
+                           dense products on the fp32-input MFMA (csrc/sp_svd_sep.hip).
+                           The maps need a workspace: sp_op_apply_ws = A, sp_op_vjp_ws =
+                           A^T, sp_op_pinv_ws = A^+ / A^+T, the fused DPS, PGDM, proximal
+                           and DDRM passes as PSF_PERIODIC                           */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -172,19 +183,35 @@ typedef struct sp_op {
                                         the host.  Preconditions: |alpha| >= 1,
                                         |beta| <= 1, length finite, axis 0 or 1 (other
                                         values stay in bounds, the result is then
-                                        unspecified)                             */
+                                        unspecified).  SVD_SEPARABLE: six row-major
+                                        tables back to back, H*H + W*W + Hy*Hy +
+                                        Wy*Wy + 2*Hy*Wy floats: V_H[H][H] and
+                                        V_W[W][W], full orthogonal, column c the c-th
+                                        right singular vector of A_H (A_W) by
+                                        descending singular value, the null-space
+                                        completion after them; U_H[Hy][Hy] and
+                                        U_W[Wy][Wy], orthogonal, column c the c-th
+                                        left singular vector; S[Hy][Wy] = s_H[i] *
+                                        s_W[j]; P[Hy][Wy] = 1 / S on the kept set, 0
+                                        elsewhere.  Computed in fp64 by the caller
+                                        and rounded to fp32; the map is defined by
+                                        these fp32 tables taken as exact, the library
+                                        does not read them on the host              */
     int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
                                         zero rows added above and below.  PSF_FFT:
                                         1..min(height, width) - 1.  PSF_PERIODIC:
                                         1..(min(height, width) - 1) / 2.  SR_PERIODIC:
                                         the taps per axis K, factor..min(height,
                                         width), K - factor even.  RADON: the
-                                        number of angles, 1..512                 */
+                                        number of angles, 1..512.  SVD_SEPARABLE: Hy,
+                                        the rows of y, 1..height                 */
     int32_t factor;                  /* SR, SR_PERIODIC: 2, 4 or 8.  PHASE: pad_w >= 0, zero
                                         columns added left and right.  PSF_FFT: the
                                         boundary: 0 reflect, 1 circular, 2 zeros (0
                                         for the other kinds).  RADON: the number of
-                                        detector bins, 1..1024.  PHASE: keep_bits,
+                                        detector bins, 1..1024.  SVD_SEPARABLE: Wy, the
+                                        columns of y, 1..width (keep_bits and
+                                        word_rank NULL).  PHASE: keep_bits,
                                         word_rank and taps must be NULL; PSF_FFT
                                         PSF_PERIODIC and SR_PERIODIC: keep_bits and word_rank;
                                         RADON: keep_bits and word_rank too       */
@@ -279,7 +306,11 @@ int sp_debug_selftest(sp_stream_t stream);
  * n == channels*height*width, m * factor^2 == n and keep_bits and word_rank are NULL.  RADON: the
  * workgroups per sample of its project launch, channels * radius * ceil(factor / 256) (csrc/sp_radon.hip);
  * rejected unless taps != NULL, 1 <= radius <= 512, 1 <= factor <= 1024, 8 <= height, width <= 512,
- * n == channels*height*width, m == channels*radius*factor and keep_bits and word_rank are NULL. */
+ * n == channels*height*width, m == channels*radius*factor and keep_bits and word_rank are NULL.
+ * SVD_SEPARABLE: the 64 x 64 tiles of the observed grid per sample, channels * ceil(Hy / 64) *
+ * ceil(Wy / 64) (csrc/sp_svd_sep.hip); rejected unless taps != NULL, 2 <= height, width <= 512,
+ * 1 <= radius (Hy) <= height, 1 <= factor (Wy) <= width, n == channels*height*width,
+ * m == channels*Hy*Wy and keep_bits and word_rank are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
 /* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
  * 0 for every kind but those below (one pass, no workspace), batch * m for PSF (its residual launch
@@ -287,12 +318,15 @@ int64_t sp_rsq_partials(const sp_op* op);
  * PHASE (the complex row transforms, stored transposed), 2 * batch * channels * (Nw/2 + 1) * height
  * for PSF_FFT (the same, half the spectrum: the rows are real) and for PSF_PERIODIC and SR_PERIODIC
  * (Nw = width),
- * batch * m for RADON (grad_scale * r in sinogram space, between project and backproject).  SP_EINVAL for a rejected
+ * batch * m for RADON (grad_scale * r in sinogram space, between project and backproject),
+ * 3 * batch * n for SVD_SEPARABLE (two intermediates of the per-side products and T_y(y)).  SP_EINVAL for a rejected
  * descriptor or batch <= 0.  The library allocates nothing. */
 int64_t sp_dps_workspace(const sp_op* op, int64_t batch);
 /* Floats of `work` that sp_op_apply_ws / sp_op_vjp_ws need: 0 for the linear kinds, the figure
  * of sp_dps_workspace for PHASE, PSF_FFT, PSF_PERIODIC and SR_PERIODIC (sp_op_pinv_ws and
- * sp_pgdm_residual_ws take the same).  SP_EINVAL for a rejected descriptor or batch <= 0. */
+ * sp_pgdm_residual_ws take the same), 2 * batch * n for SVD_SEPARABLE (two intermediates; the
+ * same for sp_op_pinv_ws, sp_pgdm_residual_ws and the proximal entries).  SP_EINVAL for a rejected
+ * descriptor or batch <= 0. */
 int64_t sp_op_workspace(const sp_op* op, int64_t batch);
 
 /* What the kind of `op` does at the entry points below, as bits; 0 for a rejected descriptor.
@@ -335,7 +369,12 @@ int sp_dps_residual(const sp_op* op, const float* x, const float* eps, const flo
  * column launch with M, which stores the height / factor lattice rows alone; per tile of lattice
  * rows the inverse row FFT, g = grad_scale * (y - A x0) on the lattice columns, one r^2 partial,
  * g zero-inserted along the row and transformed forward; the column launch that inserts the zero
- * rows in LDS, with conj(M); inverse row FFTs -> v = A^T g.  RADON runs here only too, as two launches
+ * rows in LDS, with conj(M); inverse row FFTs -> v = A^T g.  SVD_SEPARABLE runs here only too, as
+ * six launches of one per-plane product kernel on the fp32-input MFMA (csrc/sp_svd_sep.hip):
+ * U_H^T y and its product with U_W -> yhat = T_y(y) per observation row; V_H[:, :Hy]^T x0 (x0 formed in
+ * the loads); its product with V_W[:, :Wy] with the epilogue r = yhat - S d, one r^2 partial per
+ * 64 x 64 tile, g = grad_scale * (S r) (U is orthogonal, so |y - A x0| = |r|); V_H[:, :Hy] g; its
+ * product with V_W[:, :Wy]^T -> v = A^T(grad_scale (y - A x0)).  RADON runs here only too, as two launches
  * (csrc/sp_radon.hip): `project` forms x0 while it stages its slab of the plane, sums every ray in
  * row (column) order, writes work = grad_scale * (y - A x0) and one |r|^2 partial per workgroup;
  * `backproject` gathers v = A^T work per pixel, angles in order.  The result has the same bits on
@@ -400,12 +439,15 @@ int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, flo
  * or inf).  PSF_FFT: dx = A^T g, the exact adjoint (x is not read); PSF_PERIODIC the same, with
  * the multiplier conj(M); SR_PERIODIC: dx = Re IFFT2(FFT2(up g) * conj(M)), up the zero insertion
  * onto the lattice (only the lattice rows are read and row-transformed; the column launch inserts
- * the zero rows in LDS).  SP_EUNSUPPORTED for the
+ * the zero rows in LDS).  SVD_SEPARABLE: sp_op_apply_ws is y = U_H (S * (V_H^T x V_W)[:Hy, :Wy])
+ * U_W^T and sp_op_vjp_ws its exact transpose dx = V_H[:, :Hy] (S * (U_H^T g U_W)) V_W[:, :Wy]^T, four
+ * launches each (one per side and transform, the multiplier in the second one's epilogue).
+ * SP_EUNSUPPORTED for the
  * linear kinds without a workspace, whose VJP is sp_op_adjoint. */
 int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
                  float* work, sp_stream_t stream);
 
-/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC, SR_PERIODIC); SP_EUNSUPPORTED for every other kind, SP_EINVAL
+/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC, SR_PERIODIC, SVD_SEPARABLE); SP_EUNSUPPORTED for every other kind, SP_EINVAL
  * for a rejected descriptor or argument first.  No reference counterpart: the reference's
  * SVDOperator.apply_pseudo_inverse (linear.py) is the dense form of the same map.
  *   sp_op_pinv_ws        x = A^+ y = Re IFFT2(FFT2(y) * P) (transpose = 0) or A^+T y (transpose =
@@ -429,6 +471,13 @@ int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int
  * strided as above: the residual is formed on the lattice, where y is 2 factor^2 times smaller
  * than a spectrum of up y); sp_pgdm_residual_ws is v = grad_scale * A^+ (y - A x0) in the five
  * launches of its DPS pass 1 with P in the second column launch and no partials.
+ * SVD_SEPARABLE: sp_op_pinv_ws is the launches of sp_op_vjp_ws (transpose = 0: x = A^+ y) or of
+ * sp_op_apply_ws (transpose = 1: A^+T) with P in S's place.  sp_pgdm_prepare writes q = P * T_y(y),
+ * T_y(Y) = U_H^T Y U_W, per observation row: q has sp_op_workspace(op, rows) = 2 * rows * n floats,
+ * a row every 2 n floats, whose first m floats hold q as [channels][Hy][Wy] and whose next m the
+ * launches' intermediate; two launches.  sp_pgdm_residual_ws is
+ * v = grad_scale * T^-1[q - K * T(x0)] with T(X) = V_H^T X V_W on the observed grid and K = (P != 0),
+ * i.e. grad_scale * (A^+ y - Pi x0), in four launches (the subtraction in the second one's epilogue).
  * work and q must not alias any other argument. */
 int sp_op_pinv_ws(const sp_op* op, const float* y, float* x, int64_t batch, int32_t transpose,
                   float* work, sp_stream_t stream);
@@ -448,6 +497,9 @@ int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const
  *   PSF_PERIODIC (A = IFFT2 M FFT2)       Z = (conj(M) Y + rho X0) / (|M|^2 + rho), z = Re IFFT2(Z).
  *   SR_PERIODIC (A A^T diagonal, Lambda)  z = x0 + Re IFFT2(FFT2(up r) conj(M) / (Lambda_t + rho)):
  *                                         every frequency divided, not only the kept ones;
+ *   SVD_SEPARABLE (A = U S V_obs^T)       Z = (S * T_y(y) + rho T(x0)) / (S^2 + rho) on the observed
+ *                                         grid, T(x0) itself outside it (a select), z = T^-1 Z: exact
+ *                                         for the full A, every component divided.
  * Every other kind: SP_EUNSUPPORTED (after the common argument checks, which answer SP_EINVAL).
  * The scalars are applied as reciprocals computed once per thread (1 / a, 1 / k, 1 / (1 + rho s^2),
  * 1 / (|M|^2 + rho)), as sp_dps_update does.  Plain stores, no atomics; every sample is computed
@@ -461,12 +513,14 @@ typedef struct sp_prox_coefs {
     float c_xi;   /* sqrt(1 - alpha_bar[t_prev]) * sqrt(zeta)                 */
 } sp_prox_coefs;  /* 24 bytes */
 /* Floats of `work` that sp_op_prox_ws / sp_diffpir_step_ws need for `batch` samples: 0 for the
- * elementwise kinds and SR, the sp_op_workspace figure for PSF_PERIODIC and SR_PERIODIC.  This is the capability
+ * elementwise kinds and SR, the sp_op_workspace figure for PSF_PERIODIC, SR_PERIODIC and SVD_SEPARABLE.  This is the capability
  * probe: SP_EUNSUPPORTED for a valid kind without a closed-form prox, SP_EINVAL for a rejected
  * descriptor or batch <= 0. */
 int64_t sp_prox_workspace(const sp_op* op, int64_t batch);
 /* Floats of `q` for `rows` observation rows: 0 but for PSF_PERIODIC and SR_PERIODIC,
- * 2 * rows * channels * (width/2 + 1) * height there.  Codes as sp_prox_workspace. */
+ * 2 * rows * channels * (width/2 + 1) * height there, and SVD_SEPARABLE, 2 * rows * n (a row every
+ * 2 n floats: q = S * T_y(y) in the first m, the launches' intermediate after it).  Codes as
+ * sp_prox_workspace. */
 int64_t sp_prox_prepare_size(const sp_op* op, int64_t rows);
 /* q = conj(M) * FFT2(y) / (H W) per observation row, as (re, im) pairs
  * [row][channels][width/2 + 1][height] (the intermediate's layout): sp_pgdm_prepare's two launches
@@ -479,7 +533,10 @@ int sp_prox_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_
  * FFTs of x0 -> work; per column tile z <- (q[b / y_div] + rho z / (H W)) / (|M|^2 + rho) between
  * the transforms; inverse row FFTs, real part -> z_out; q and work required, y not read) or five
  * (SR_PERIODIC: its DPS pass 1 with grad_scale = 1, no partials and conj(M) / (Lambda_t + rho) in
- * the second column launch; the last launch adds x0 in space; q and work required, y not read).
+ * the second column launch; the last launch adds x0 in space; q and work required, y not read) or four
+ * (SVD_SEPARABLE: V_H^T x0; its product with V_W with the quotient in the epilogue; V_H times that;
+ * the product with V_W^T, in the step form with the DiffPIR update and the noise tile in its
+ * epilogue; q and work required, y not read).
  * z_out may alias x0; work and q must not alias any other argument. */
 int sp_op_prox_ws(const sp_op* op, const float* x0, const float* y, const float* q, int64_t batch,
                   int64_t y_div, float rho, float* z_out, float* work, sp_stream_t stream);
@@ -511,7 +568,8 @@ int sp_diffpir_step_ws(const sp_op* op, const float* x, const float* eps, const 
  * becomes noise and the fp32 recurrence leaves every bound.  y = A x0 gives
  * gamma0 = 0, iters = 0 and z = x0 bit for bit.  A and A^T are the kind's own maps (sp_op_apply /
  * sp_op_adjoint, or sp_op_apply_ws / sp_op_vjp_ws for the kinds whose maps need a workspace).
- * Kinds: IDENTITY, INPAINT, MASK, BLUR, SR, PSF, RADON, PSF_FFT, PSF_PERIODIC, SR_PERIODIC; PHASE
+ * Kinds: IDENTITY, INPAINT, MASK, BLUR, SR, PSF, RADON, PSF_FFT, PSF_PERIODIC, SR_PERIODIC,
+ * SVD_SEPARABLE; PHASE
  * (nonlinear): SP_EUNSUPPORTED, after the argument checks.
  * A call is one launch sequence of fixed length, max_iter x (A, A^T and four vector launches; the
  * last iteration three), whatever the samples do: alpha, beta, gamma, delta and iters stay on the
@@ -579,6 +637,12 @@ int sp_diffpir_step_cg_ws(const sp_op* op, const float* x, const float* eps, con
  *                                        (s = |M| where P != 0, unobserved elsewhere; q as
  *                                        sp_pgdm_prepare writes it), one inverse column transform;
  *                                        inverse rows, real part, times a_prev.
+ *   SVD_SEPARABLE (V^T = T)              four launches through work: V_H^T of x0, eps and xi (read, or
+ *                                        drawn by Philox in the loads) in one launch; their products
+ *                                        with V_W with F = f_y q + f_th X0 + f_eps E + f_xi Xi in the
+ *                                        epilogue (s = S where P != 0 on the observed grid, unobserved
+ *                                        elsewhere; q as sp_pgdm_prepare writes it); V_H F; its product
+ *                                        with V_W^T times a_prev.
  * Every other kind: SP_EUNSUPPORTED.  1 / a is taken once per thread.  Plain stores, no atomics;
  * every sample is computed alone, so the bits do not depend on the batch, y_div or the shard. */
 typedef struct sp_ddrm_coefs {
@@ -592,12 +656,13 @@ typedef struct sp_ddrm_coefs {
     float c1;       /* sqrt(1 - eta^2), computed in fp64 by the caller         */
 } sp_ddrm_coefs;    /* 32 bytes */
 /* Floats of `work` that sp_ddrm_step_ws needs for `batch` samples: 0 for the one-launch kinds,
- * three intermediates (3 * sp_op_workspace) for PSF_PERIODIC.  This is the capability probe:
+ * three intermediates (3 * sp_op_workspace) for PSF_PERIODIC, 4 * batch * n for SVD_SEPARABLE (the
+ * three transformed sources and the combined spectrum).  This is the capability probe:
  * SP_EUNSUPPORTED for a valid kind without a DDRM step (BLUR, PSF, PHASE, PSF_FFT, RADON,
  * SR_PERIODIC), SP_EINVAL for a rejected descriptor or batch <= 0. */
 int64_t sp_ddrm_workspace(const sp_op* op, int64_t batch);
-/* The whole DDRM step after the network call.  q: PSF_PERIODIC reads what sp_pgdm_prepare wrote
- * (P FFT2(y) / (H W), row b / y_div) and not y; the one-launch kinds read y and q may be NULL.
+/* The whole DDRM step after the network call.  q: PSF_PERIODIC and SVD_SEPARABLE read what
+ * sp_pgdm_prepare wrote (P FFT2(y) / (H W), or P T_y(y); row b / y_div) and not y; the one-launch kinds read y and q may be NULL.
  * xi: injected standard normals (batch * n) or NULL to draw the Philox normals of sp_randn,
  * (seed, step, sample_offset + b, flat element index).  x_out may alias x; work aliases nothing.
  * SP_EINVAL: a null x, eps, coefs or x_out; a null y (or q) or work where it is read; batch <= 0

@@ -613,12 +613,22 @@ static constexpr op_kind g_kinds[] = {
      .pgdm_residual = sr_periodic_pgdm_residual, .prox_workspace = psf_fft_workspace,
      .prox_prepare = sr_periodic_prox_prepare, .prox = sr_periodic_prox,
      .diffpir_step = sr_periodic_prox},
+    /* SP_OP_SVD_SEPARABLE: every column of PSF_PERIODIC on the SVDs of the two 1-D factors, as
+       per-plane dense products; y of (C, Hy, Wy) */
+    {.valid = svd_sep_valid, .partials = svd_sep_partials, .dps_workspace = svd_sep_dps_workspace,
+     .op_workspace = svd_sep_op_workspace, .dps_residual = svd_sep_dps_residual,
+     .apply_ws = svd_sep_apply, .vjp_ws = svd_sep_vjp,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
+     .pinv_ws = svd_sep_pinv, .pgdm_prepare = svd_sep_pgdm_prepare,
+     .pgdm_residual = svd_sep_pgdm_residual, .prox_workspace = svd_sep_op_workspace,
+     .prox_prepare = svd_sep_prox_prepare, .prox = svd_sep_prox, .diffpir_step = svd_sep_prox,
+     .ddrm_workspace = svd_sep_ddrm_workspace, .ddrm_step = svd_sep_ddrm},
 };
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
                   SP_OP_PSF_PERIODIC == 8 && SP_OP_RADON == 9 && SP_OP_SR_PERIODIC == 10 &&
-                  kKinds == 11,
+                  SP_OP_SVD_SEPARABLE == 11 && kKinds == 12,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -636,7 +646,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 112; }
+int sp_version(void) { return 113; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 

@@ -168,5 +168,17 @@ pinv_ws_fn sr_periodic_pinv;
 pgdm_prepare_fn sr_periodic_pgdm_prepare, sr_periodic_prox_prepare;
 pgdm_residual_fn sr_periodic_pgdm_residual;
 prox_fn sr_periodic_prox;
+// SP_OP_SVD_SEPARABLE (sp_svd_sep.hip: per-plane dense products on the fp32-input MFMA)
+valid_fn svd_sep_valid;
+partials_fn svd_sep_partials;
+workspace_fn svd_sep_op_workspace, svd_sep_dps_workspace, svd_sep_ddrm_workspace;
+dps_residual_fn svd_sep_dps_residual;
+apply_ws_fn svd_sep_apply;
+vjp_ws_fn svd_sep_vjp;
+pinv_ws_fn svd_sep_pinv;
+pgdm_prepare_fn svd_sep_pgdm_prepare, svd_sep_prox_prepare;
+pgdm_residual_fn svd_sep_pgdm_residual;
+prox_fn svd_sep_prox;  // both forms: p.eps selects
+ddrm_fn svd_sep_ddrm;
 
 }  // namespace sp

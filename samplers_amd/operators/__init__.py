@@ -20,6 +20,7 @@ from .radon import RadonOperator, radon_table
 from .sr_filter import BicubicSuperResolutionOperator, FilteredSuperResolutionOperator, bicubic_taps
 from .sr_periodic import PeriodicSuperResolutionOperator
 from .superres import SuperResolutionOperator
+from .svd_separable import SeparableSVDOperator
 
 __all__ = [
     "Operator",
@@ -43,6 +44,7 @@ __all__ = [
     "MotionBlurOperator",
     "FFTPSFBlurOperator",
     "PeriodicBlurOperator",
+    "SeparableSVDOperator",
     "PhaseRetrievalOperator",
     "RadonOperator",
     "radon_table",

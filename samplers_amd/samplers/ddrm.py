@@ -27,8 +27,10 @@ schedule asks for.  The class is decided by the one fp32 expression
 ``(σ'·σ')·s² ≥ σ_y·σ_y``.
 
 The fused path (``sp_ddrm_workspace`` is the probe) serves the identity, inpainting / mask,
-×s average-pooling super-resolution and the periodic blur; any other ``SVDOperator`` without a
-HIP descriptor takes ``ddrm_step_svd``, the same step in plain torch through its factors; the rest
+×s average-pooling super-resolution, the periodic blur and the separable-SVD operator (any blur
+or filtered super-resolution of the form ``A_H X A_Wᵀ``); any other ``SVDOperator`` without a
+HIP descriptor takes ``ddrm_step_svd``, the same step in plain torch through its factors (so does
+the separable-SVD operator on host tensors); the rest
 raise ``NotImplementedError``.  The noise model must be ``GaussianNoise`` unless ``noise_std`` is
 given.  The run starts from ``initial_sample`` rather than DDRM's spectral initialisation: at
 ``ᾱ_T ≈ 4e-5`` the two coincide.  Noise sources (``rng`` / ``seed`` / ``noise_fn``) are
@@ -56,7 +58,7 @@ from samplers_amd.samplers.utils.bridge_kernels import (DDRMCoefficients, ddrm_c
 Condition_co = TypeVar("Condition_co", covariant=True)
 
 SUPPORTED = ("IdentityOperator, InpaintingOperator (and subclasses), SuperResolutionOperator, "
-             "PeriodicBlurOperator, or an SVDOperator without a HIP descriptor "
+             "PeriodicBlurOperator, SeparableSVDOperator, or an SVDOperator without a HIP descriptor "
              "(GeneralSVDOperator)")
 
 
@@ -136,15 +138,18 @@ class FusedDDRMStep(FusedStep):
                              f"noise_std, got {type(noise).__name__}")
         super().__init__(network, op, y_div, micro_batch, timer)
         self.desc = ddrm_descriptor(op)
-        self.fused = self.desc is not None
+        # an SVDOperator with a fused step still runs through its factors on host tensors
+        host_svd = (self.desc is not None and isinstance(op, SVDOperator)
+                    and not observation_rows.is_cuda)
+        self.fused = self.desc is not None and not host_svd
         if not self.fused:
-            if not isinstance(op, SVDOperator) or _hip.descriptor_of(op) is not None:
+            if not isinstance(op, SVDOperator) or not (host_svd or _hip.descriptor_of(op) is None):
                 raise NotImplementedError(
                     f"{type(op).__name__} has no DDRM step: DDRMSampler supports {SUPPORTED}")
             self.y = observation_rows
             return
         self._bind_rows(observation_rows, "DDRMSampler")
-        if int(self.lib.sp_ddrm_workspace(self.desc, 1)) > 0:  # the periodic kind: Q = P FFT2(y) / (H W)
+        if int(self.lib.sp_ddrm_workspace(self.desc, 1)) > 0:  # the spectral kinds: q = P T_y(y), once
             self._prepare_q("sp_op_workspace", "sp_pgdm_prepare")
 
     def coefficients(self, t: int, t_prev: int) -> DDRMCoefficients:

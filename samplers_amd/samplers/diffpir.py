@@ -36,7 +36,8 @@ from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.networks.base import EpsilonNetwork, host_alphas_cumprod
 from samplers_amd.noise import GaussianNoise
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.dps import FusedStep, KernelTimer, NoiseFn
+from samplers_amd.samplers.dps import (FusedStep, KernelTimer, NoiseFn, host_noise, host_predict_x0,
+                                       host_svd_operator)
 from samplers_amd.samplers.loop import run_sampler
 from samplers_amd.samplers.utils.bridge_kernels import diffpir_coefficients
 
@@ -52,8 +53,8 @@ def prox_descriptor(operator) -> "_hip.SpOp":
         raise NotImplementedError(
             f"{type(operator).__name__} has no closed-form proximal map (apply_prox): DiffPIR "
             "supports IdentityOperator, InpaintingOperator (and subclasses), "
-            "SuperResolutionOperator, PeriodicBlurOperator and "
-            "PeriodicSuperResolutionOperator")
+            "SuperResolutionOperator, PeriodicBlurOperator, "
+            "PeriodicSuperResolutionOperator and SeparableSVDOperator")
     return desc
 
 
@@ -110,6 +111,11 @@ class FusedDiffPIRStep(FusedStep):
         self.desc = cg_descriptor(op) if self.cg else prox_descriptor(op)
         self.iterations: Tensor | None = None
         super().__init__(network, op, y_div, micro_batch, timer)
+        # an SVDOperator with HIP kernels runs through its host maps on host tensors
+        self.host = host_svd_operator(op, observation_rows)
+        if self.host:
+            self.y = observation_rows
+            return
         self._bind_rows(observation_rows, "DiffPIRSampler")
         if not self.cg:  # conjugate gradients prepare nothing: the maps read y itself
             self._prepare_q("sp_prox_prepare_size", "sp_prox_prepare", optional=True)
@@ -134,6 +140,8 @@ class FusedDiffPIRStep(FusedStep):
                  seed: int = 0, sample_offset: int = 0) -> Tensor:
         """Advance ``x`` (flat ``(B, *x_shape)``, contiguous fp32) one step, in place."""
         coefs = self.coefficients(t, t_prev)
+        if self.host:
+            return self._host_step(x, coefs, t, host_noise(xi))
         stream = _hip.stream_of(x)
         iters = torch.zeros(x.shape[0], device=x.device, dtype=torch.int32) if self.cg else None
         for b0, b1 in self._chunks(x.shape[0]):
@@ -159,6 +167,30 @@ class FusedDiffPIRStep(FusedStep):
             self.iterations = (iters[None] if self.iterations is None
                                else torch.cat([self.iterations, iters[None]]))
         return x
+
+
+    def _host_step(self, x: Tensor, c: _hip.SpProxCoefs, t: int, xi: Tensor) -> Tensor:
+        """The step in plain torch through ``apply_prox`` / ``apply_prox_cg`` on host tensors."""
+        op = self.operator
+        iters = torch.zeros(x.shape[0], dtype=torch.int32)
+        with torch.no_grad():
+            for b0, b1 in self._chunks(x.shape[0]):
+                xc = x[b0:b1]
+                y = self.y[torch.arange(b0, b1) // self.y_div].to(xc.dtype)
+                x0 = (xc - c.k * self.network.forward(xc, t)) / c.a
+                if self.cg:
+                    z, iters[b0:b1] = op.apply_prox_cg(x0, y, c.rho, self.cg_iterations, self.cg_tol,
+                                                       return_iterations=True)
+                else:
+                    z = op.apply_prox(x0, y, c.rho)
+                xc.copy_(c.a_prev * z + (c.c_eps * ((xc - c.a * z) * (1.0 / c.k)) + c.c_xi * xi[b0:b1]))
+        if self.cg:
+            self.iterations = (iters[None] if self.iterations is None
+                               else torch.cat([self.iterations, iters[None]]))
+        return x
+
+    def predict_x0(self, x: Tensor, t: int) -> Tensor:
+        return host_predict_x0(self, x, t) if self.host else super().predict_x0(x, t)
 
 
 class DiffPIRSampler(PosteriorSampler, Generic[Condition_co]):

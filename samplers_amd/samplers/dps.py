@@ -189,7 +189,7 @@ class FusedDPSStep(FusedStep):
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
                 "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses), "
                 "FFTPSFBlurOperator, PeriodicBlurOperator, PeriodicSuperResolutionOperator, "
-                "RadonOperator and PhaseRetrievalOperator"
+                "SeparableSVDOperator, RadonOperator and PhaseRetrievalOperator"
             )
         super().__init__(network, op, y_div, micro_batch, timer)
         self._bind_rows(observation_rows, "DPSSampler")
@@ -408,9 +408,73 @@ def native_plugins(inverse_problem) -> bool:
     return gs() is not None
 
 
+def host_svd_operator(operator, observation: Tensor) -> bool:
+    """An ``SVDOperator`` with HIP kernels whose observation lives on the host: its maps are plain
+    torch there, so PGDM, DiffPIR and DDRM run it in torch (set-up and reference runs)."""
+    from samplers_amd.operators.linear import SVDOperator
+
+    return (isinstance(operator, SVDOperator) and _hip.descriptor_of(operator) is not None
+            and not observation.is_cuda)
+
+
+def host_predict_x0(step: FusedStep, x: Tensor, t: int) -> Tensor:
+    """``predict_x0`` in plain torch: the prior's forward and ``(x − k·eps)/a``."""
+    a, k = x0_coefficients(host_alphas_cumprod(step.network), t)
+    out = torch.empty_like(x)
+    for b0, b1 in step._chunks(x.shape[0]):
+        with torch.no_grad():
+            out[b0:b1] = (x[b0:b1] - k * step.network.forward(x[b0:b1], t)) / a
+    return out
+
+
+def host_noise(xi: Tensor | None) -> Tensor:
+    if xi is None:
+        raise ValueError("rng='philox' draws on the device; on host tensors pass rng='torch' or a "
+                         "noise_fn")
+    return xi
+
+
+class HostPGDMStep(FusedStep):
+    """One PGDM iteration on host tensors for ``host_svd_operator``s (``pgdm.py:104-135`` as
+    written): x̂₀, the gradient of ‖A⁺y − A⁺A x̂₀‖² in the sample by autograd through the prior and
+    the operator's host maps, the bridge update in torch.  The device path is ``FusedDPSStep``."""
+
+    def __init__(self, network: EpsilonNetwork, inverse_problem: InverseProblem,
+                 observation_rows: Tensor, y_div: int, *, eta: float = 1.0,
+                 micro_batch: int | None = None, timer: KernelTimer | None = None,
+                 guidance_weight: float = 1.0, **_unused) -> None:
+        super().__init__(network, inverse_problem.operator, y_div, micro_batch, timer)
+        self.y = observation_rows
+        self.eta, self.guidance_weight = float(eta), float(guidance_weight)
+
+    def __call__(self, x: Tensor, step: int, t: int, t_prev: int, s: int, *,
+                 xi: Tensor | None = None, seed: int = 0, sample_offset: int = 0) -> Tensor:
+        xi, op = host_noise(xi), self.operator
+        acp = host_alphas_cumprod(self.network)
+        a, k = x0_coefficients(acp, t)
+        br = bridge_coefficients(acp, ell=t, t=t_prev, s=s, eta=self.eta)
+        for b0, b1 in self._chunks(x.shape[0]):
+            xc = x[b0:b1]
+            y = self.y[torch.arange(b0, b1) // self.y_div].to(xc.dtype)
+            with torch.enable_grad():
+                xr = xc.detach().requires_grad_(True)
+                x0 = (xr - k * self.network.forward(xr, t)) / a
+                loss = (op.apply_pseudo_inverse(y) - op.apply_pseudo_inverse(op.apply(x0))).pow(2).sum()
+                (grad,) = torch.autograd.grad(loss, xr)
+            with torch.no_grad():
+                xc.copy_(br.c_ell * xc + br.c_s * x0.detach() + br.std * xi[b0:b1]
+                         - self.guidance_weight * k * grad)
+        return x
+
+    def predict_x0(self, x: Tensor, t: int) -> Tensor:
+        return host_predict_x0(self, x, t)
+
+
 def make_dps_step(network, inverse_problem, observation_rows, y_div, **kw):
     """The fused HIP step for native plugins, the generic-plugin step otherwise."""
     mode = kw.get("mode", "dps")
+    if mode == "pgdm" and host_svd_operator(inverse_problem.operator, observation_rows):
+        return HostPGDMStep(network, inverse_problem, observation_rows, y_div, **kw)
     native_op = _hip.descriptor_of(inverse_problem.operator) is not None
     if (mode == "dps" and native_plugins(inverse_problem)) or (mode == "pgdm" and native_op):
         return FusedDPSStep(network, inverse_problem, observation_rows, y_div, **kw)

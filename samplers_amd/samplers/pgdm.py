@@ -8,7 +8,9 @@ prior's input-VJP gives w = Jᵀv, and pass 2 writes
 ``ddim_step(x, x0) − guidance_weight·sqrt(1−ᾱ_t)·(v − k w)/a``.
 ``PeriodicBlurOperator`` has a pseudo-inverse of its own (a per-frequency division): its pass 1
 is ``sp_pgdm_residual_ws``, v = −2 (A⁺y − A⁺A x0), over Q = P ⊙ FFT2(y) prepared once per call.
-``PeriodicSuperResolutionOperator`` likewise (v = −2 A⁺(y − A x0), q holding y itself).
+``PeriodicSuperResolutionOperator`` likewise (v = −2 A⁺(y − A x0), q holding y itself), and
+``SeparableSVDOperator`` (v = −2 (A⁺y − Π x0) through the SVDs of its two factors, q = P ⊙ U_Hᵀ y U_W;
+on host tensors ``HostPGDMStep``, the reference's loop body in plain torch through its host maps).
 Operators without ``apply_pseudo_inverse`` raise ``NotImplementedError`` as in
 the reference (``pgdm.py:56-66``).
 """
@@ -22,7 +24,7 @@ from torch import Tensor
 
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.samplers.base import PosteriorSampler
-from samplers_amd.samplers.dps import KernelTimer, NoiseFn, make_dps_step
+from samplers_amd.samplers.dps import KernelTimer, NoiseFn, host_svd_operator, make_dps_step
 from samplers_amd.samplers.loop import run_sampler
 
 Condition_co = TypeVar("Condition_co", covariant=True)
@@ -70,5 +72,7 @@ class PGDMSampler(PosteriorSampler, Generic[Condition_co]):
         return run_sampler(self, inverse_problem, make_step, num_sampling_steps=num_sampling_steps,
                            num_reconstructions=num_reconstructions, condition=condition, rng=rng,
                            seed=seed, noise_fn=noise_fn, sample_offset=sample_offset,
-                           keep_reconstruction_dim=keep_reconstruction_dim, require="PGDMSampler",
-                           anchored=True)
+                           keep_reconstruction_dim=keep_reconstruction_dim,
+                           # an SVDOperator with HIP kernels runs through its host maps on host tensors
+                           require=None if host_svd_operator(operator, inverse_problem.observation)
+                           else "PGDMSampler", anchored=True)
