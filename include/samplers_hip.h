@@ -115,7 +115,7 @@ enum {
                            workspace: sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
                            sp_op_pinv_ws = A^+ / A^+T, and the fused PGDM and prox
                            passes as PSF_PERIODIC                                 */
-    SP_OP_SVD_SEPARABLE = 11 /* new: A X = A_H X A_W^T on every channel plane, A_H (Hy x H)
+    SP_OP_SVD_SEPARABLE = 11, /* new: A X = A_H X A_W^T on every channel plane, A_H (Hy x H)
                            and A_W (Wy x W) any dense matrices (a blur under any boundary
                            rule, filter-and-decimate super-resolution), given by their
                            SVDs: A = (U_H (x) U_W) diag(s_H[i] s_W[j]) (V_H (x) V_W)^T.  y is
@@ -126,6 +126,32 @@ enum {
                            The maps need a workspace: sp_op_apply_ws = A, sp_op_vjp_ws =
                            A^T, sp_op_pinv_ws = A^+ / A^+T, the fused DPS, PGDM, proximal
                            and DDRM passes as PSF_PERIODIC                           */
+    SP_OP_HADAMARD = 12 /* new: compressed sensing on a scrambled Walsh-Hadamard transform.  Per
+                           channel plane, with i = h*width + w and n_p = height*width = 2^k,
+                           (A x)[c][r] = n_p^(-1/2) sum_i (-1)^popcount(j_r & i) d[i] x[c][i]:
+                           j_r the r-th kept coefficient in ascending natural (Sylvester)
+                           order, d the sign vector in taps (n_p floats, each exactly +-1;
+                           NULL: all +1), the kept set and d shared by the channels.
+                           keep_bits (n_p / 64 words, bit j%64 of word j/64 set <=>
+                           coefficient j observed) and word_rank (the observed count before
+                           word w) as INPAINT over one plane, both non-null; radius = factor
+                           = 0; 6 <= k <= 20, height, width >= 1; n = channels*n_p;
+                           m % channels == 0 and 1 <= m/channels <= n_p; y is (channels,
+                           m/channels).  A A^T = I_m and A^+ = A^T (U = I, s = 1, V^T the
+                           transform).  n_p^(-1/2) is applied once per transform: a power of
+                           two for even k, the fp32 rounding of 2^(-k/2) for odd k.
+                           csrc/sp_hadamard.hip: add/subtract levels in LDS, one launch per
+                           map for n_p <= 4096, else a low stage (chunks of 4096 floats), a
+                           high stage (all high rows by a run of columns) through work.  The
+                           maps need a workspace: sp_op_apply_ws = A, sp_op_vjp_ws = A^T,
+                           sp_op_pinv_ws = A^T / A; the fused DPS, PGDM, proximal, DiffPIR
+                           and DDRM passes are out = base + A^T(g y + A w) in one launch
+                           (n_p <= 4096) or three; every workspace (sp_dps_workspace,
+                           sp_op_workspace, sp_prox_workspace, sp_ddrm_workspace) is
+                           batch * n floats; sp_rsq_partials is channels * (1 or the high
+                           stage's tiles per plane); the q of sp_pgdm_prepare is y copied,
+                           rows of m floats (sp_pgdm_residual_ws and sp_ddrm_step_ws read
+                           it), sp_prox_prepare prepares nothing: the prox entries read y */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -137,7 +163,9 @@ typedef struct sp_op {
     int64_t m;                       /* elements per y sample                 */
     const uint64_t* keep_bits;       /* INPAINT: ceil(n/64) words; bit (j%64) of
                                         word j/64 set <=> x[j] observed (= ~mask) */
-    const int32_t* word_rank;        /* INPAINT: observed count before word w  */
+    const int32_t* word_rank;        /* INPAINT: observed count before word w.
+                                        HADAMARD: both over one plane's n_p
+                                        coefficients, shared by the channels      */
     const float* taps;               /* BLUR: 2*radius+1 normalised taps.  PSF: the
                                         dense row-major (2*radius+1)^2 taps, used
                                         as given (any finite values).  PSF_FFT: the
@@ -447,7 +475,7 @@ int sp_op_apply_ws(const sp_op* op, const float* x, float* y, int64_t batch, flo
 int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int64_t batch,
                  float* work, sp_stream_t stream);
 
-/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC, SR_PERIODIC, SVD_SEPARABLE); SP_EUNSUPPORTED for every other kind, SP_EINVAL
+/* The kinds with SP_TRAIT_PINV (PSF_PERIODIC, SR_PERIODIC, SVD_SEPARABLE, HADAMARD: A^+ = A^T, q = y); SP_EUNSUPPORTED for every other kind, SP_EINVAL
  * for a rejected descriptor or argument first.  No reference counterpart: the reference's
  * SVDOperator.apply_pseudo_inverse (linear.py) is the dense form of the same map.
  *   sp_op_pinv_ws        x = A^+ y = Re IFFT2(FFT2(y) * P) (transpose = 0) or A^+T y (transpose =

@@ -32,6 +32,9 @@ SP_OP_SR_PERIODIC = 10
 # A X = A_H X A_W^T per plane through the SVDs of the two factors (dense products on the fp32-input
 # MFMA): every pass of SP_OP_PSF_PERIODIC for any sizes and boundary rule, y of (C, radius, factor)
 SP_OP_SVD_SEPARABLE = 11
+# compressed sensing on a scrambled Walsh-Hadamard transform, y = S H D x per plane (butterflies in
+# LDS): a partial isometry with every pass of SP_OP_SVD_SEPARABLE, y of (C, m / C)
+SP_OP_HADAMARD = 12
 # sp_op_traits bits: what a kind does at the entry points (the library's table, not a list here)
 SP_TRAIT_UPDATE_READS_V, SP_TRAIT_DPS_WORKSPACE, SP_TRAIT_FUSED_LATENT = 1, 2, 4
 SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U, SP_TRAIT_PINV = 8, 16, 32

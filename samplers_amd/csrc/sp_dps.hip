@@ -623,12 +623,23 @@ static constexpr op_kind g_kinds[] = {
      .pgdm_residual = svd_sep_pgdm_residual, .prox_workspace = svd_sep_op_workspace,
      .prox_prepare = svd_sep_prox_prepare, .prox = svd_sep_prox, .diffpir_step = svd_sep_prox,
      .ddrm_workspace = svd_sep_ddrm_workspace, .ddrm_step = svd_sep_ddrm},
+    /* SP_OP_HADAMARD: a partial isometry (A^+ = A^T) through butterflies in LDS: the columns of
+       SVD_SEPARABLE but the prepare of the prox (its launches read y itself); q of PGDM and DDRM is
+       y copied; y of (C, m / C) */
+    {.valid = hadamard_valid, .partials = hadamard_partials, .dps_workspace = hadamard_workspace,
+     .op_workspace = hadamard_workspace, .dps_residual = hadamard_dps_residual,
+     .apply_ws = hadamard_apply, .vjp_ws = hadamard_vjp,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_DPS_WORKSPACE | SP_TRAIT_PINV,
+     .pinv_ws = hadamard_pinv, .pgdm_prepare = hadamard_pgdm_prepare,
+     .pgdm_residual = hadamard_pgdm_residual, .prox_workspace = hadamard_workspace,
+     .prox = hadamard_prox, .diffpir_step = hadamard_prox,
+     .ddrm_workspace = hadamard_workspace, .ddrm_step = hadamard_ddrm},
 };
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
                   SP_OP_PSF_PERIODIC == 8 && SP_OP_RADON == 9 && SP_OP_SR_PERIODIC == 10 &&
-                  SP_OP_SVD_SEPARABLE == 11 && kKinds == 12,
+                  SP_OP_SVD_SEPARABLE == 11 && SP_OP_HADAMARD == 12 && kKinds == 13,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -646,7 +657,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 113; }
+int sp_version(void) { return 114; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 

@@ -180,5 +180,18 @@ pgdm_prepare_fn svd_sep_pgdm_prepare, svd_sep_prox_prepare;
 pgdm_residual_fn svd_sep_pgdm_residual;
 prox_fn svd_sep_prox;  // both forms: p.eps selects
 ddrm_fn svd_sep_ddrm;
+// SP_OP_HADAMARD (sp_hadamard.hip: Walsh-Hadamard butterflies in LDS; one workspace function serves
+// every pass)
+valid_fn hadamard_valid;
+partials_fn hadamard_partials;
+workspace_fn hadamard_workspace;
+dps_residual_fn hadamard_dps_residual;
+apply_ws_fn hadamard_apply;
+vjp_ws_fn hadamard_vjp;
+pinv_ws_fn hadamard_pinv;
+pgdm_prepare_fn hadamard_pgdm_prepare;
+pgdm_residual_fn hadamard_pgdm_residual;
+prox_fn hadamard_prox;  // both forms: p.eps selects
+ddrm_fn hadamard_ddrm;
 
 }  // namespace sp

@@ -1,5 +1,6 @@
 from .base import NonlinearOperator, Operator
 from .blur import GaussianBlurOperator
+from .hadamard import HadamardOperator
 from .identity import IdentityOperator
 from .inpainting import (
     CenterInpaintingOperator,
@@ -45,6 +46,7 @@ __all__ = [
     "FFTPSFBlurOperator",
     "PeriodicBlurOperator",
     "SeparableSVDOperator",
+    "HadamardOperator",
     "PhaseRetrievalOperator",
     "RadonOperator",
     "radon_table",

@@ -27,10 +27,11 @@ schedule asks for.  The class is decided by the one fp32 expression
 ``(σ'·σ')·s² ≥ σ_y·σ_y``.
 
 The fused path (``sp_ddrm_workspace`` is the probe) serves the identity, inpainting / mask,
-×s average-pooling super-resolution, the periodic blur and the separable-SVD operator (any blur
-or filtered super-resolution of the form ``A_H X A_Wᵀ``); any other ``SVDOperator`` without a
+×s average-pooling super-resolution, the periodic blur, the separable-SVD operator (any blur
+or filtered super-resolution of the form ``A_H X A_Wᵀ``) and the Walsh–Hadamard compressed-sensing
+operator (a partial isometry: one class for its whole kept set); any other ``SVDOperator`` without a
 HIP descriptor takes ``ddrm_step_svd``, the same step in plain torch through its factors (so does
-the separable-SVD operator on host tensors); the rest
+the separable-SVD and Hadamard operators on host tensors); the rest
 raise ``NotImplementedError``.  The noise model must be ``GaussianNoise`` unless ``noise_std`` is
 given.  The run starts from ``initial_sample`` rather than DDRM's spectral initialisation: at
 ``ᾱ_T ≈ 4e-5`` the two coincide.  Noise sources (``rng`` / ``seed`` / ``noise_fn``) are
@@ -58,8 +59,8 @@ from samplers_amd.samplers.utils.bridge_kernels import (DDRMCoefficients, ddrm_c
 Condition_co = TypeVar("Condition_co", covariant=True)
 
 SUPPORTED = ("IdentityOperator, InpaintingOperator (and subclasses), SuperResolutionOperator, "
-             "PeriodicBlurOperator, SeparableSVDOperator, or an SVDOperator without a HIP descriptor "
-             "(GeneralSVDOperator)")
+             "PeriodicBlurOperator, SeparableSVDOperator, HadamardOperator, or an SVDOperator without "
+             "a HIP descriptor (GeneralSVDOperator)")
 
 
 def ddrm_descriptor(operator) -> "_hip.SpOp | None":

@@ -54,7 +54,7 @@ def prox_descriptor(operator) -> "_hip.SpOp":
             f"{type(operator).__name__} has no closed-form proximal map (apply_prox): DiffPIR "
             "supports IdentityOperator, InpaintingOperator (and subclasses), "
             "SuperResolutionOperator, PeriodicBlurOperator, "
-            "PeriodicSuperResolutionOperator and SeparableSVDOperator")
+            "PeriodicSuperResolutionOperator, SeparableSVDOperator and HadamardOperator")
     return desc
 
 

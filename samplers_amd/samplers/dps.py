@@ -189,7 +189,7 @@ class FusedDPSStep(FusedStep):
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
                 "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses), "
                 "FFTPSFBlurOperator, PeriodicBlurOperator, PeriodicSuperResolutionOperator, "
-                "SeparableSVDOperator, RadonOperator and PhaseRetrievalOperator"
+                "SeparableSVDOperator, HadamardOperator, RadonOperator and PhaseRetrievalOperator"
             )
         super().__init__(network, op, y_div, micro_batch, timer)
         self._bind_rows(observation_rows, "DPSSampler")
