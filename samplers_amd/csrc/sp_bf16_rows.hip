@@ -88,6 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_layernorm_bf16_fwd(const u16* __rest
     const int64_t r = (int64_t)blockIdx.x * LNB_ROWS + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int c8 = c >> 3;
+    SP_DCHECK(c % 8 == 0 && c8 <= NV * 64);  // the row fits the lane's registers
     float v[NV][8];
     lnb_load<NV>(x + r * c, c8, lane, v);
     float s = 0.f;
@@ -129,6 +130,7 @@ __global__ __launch_bounds__(kBlock) void k_layernorm_bf16_bwd(const u16* __rest
     const int64_t r = (int64_t)blockIdx.x * LNB_ROWS + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int c8 = c >> 3;
+    SP_DCHECK(c % 8 == 0 && c8 <= NV * 64);  // the row fits the lane's registers
     const float mu = mean[r], rs = rstd[r];
     float g[NV][8], h[NV][8];
     lnb_load<NV>(dy + r * c, c8, lane, g);

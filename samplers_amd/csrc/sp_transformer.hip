@@ -91,6 +91,7 @@ __global__ __launch_bounds__(kBlock) void k_layernorm_bwd(const float* __restric
     const int64_t r = (int64_t)blockIdx.x * LN_ROWS + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int c4 = c >> 2;
+    SP_DCHECK(c % 4 == 0 && c4 <= NV * 64);  // the row fits the lane's registers
     const float mu = mean[r], rs = rstd[r];
     float4 g[NV], h[NV];
     ln_load<NV>(dy + r * c, c4, lane, g);
@@ -178,6 +179,7 @@ __global__ __launch_bounds__(kBlock) void k_softmax_rows(float* __restrict__ s, 
     const int64_t r = (int64_t)blockIdx.x * LN_ROWS + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int n4 = n >> 2;
+    SP_DCHECK(n % 4 == 0 && n4 <= NV * 64);  // the row fits the lane's registers
     float* row = s + r * n;
     float4 v[NV];
     float mx = -INFINITY;
@@ -215,6 +217,7 @@ __global__ __launch_bounds__(kBlock) void k_softmax_bwd_rows(const float* __rest
     const int64_t r = (int64_t)blockIdx.x * LN_ROWS + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int n4 = n >> 2;
+    SP_DCHECK(n % 4 == 0 && n4 <= NV * 64);  // the row fits the lane's registers
     float4 a[NV], g[NV];
     ln_load<NV>(p + r * n, n4, lane, a);
     ln_load<NV>(dp + r * n, n4, lane, g);

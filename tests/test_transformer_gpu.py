@@ -4,7 +4,12 @@ whose gradient rides into the LayerNorm VJP (``SkipGrad`` box), and a whole
 ``BasicTransformerBlock`` forward + input VJP against the same module on the CPU (torch fp32).
 
 Tolerances: fp32 rounding of one normalisation / one erf (relative L2 < 2e-6 against fp64);
-the whole block (x6 linears, fused attention) 1e-5 relative L2 against CPU fp32."""
+the whole block (x6 linears, fused attention) 1e-5 relative L2 against CPU fp32.
+
+These are ``randn`` inputs judged by one figure per tensor.  The row kernels' edges — every
+template instantiation and 64-vector boundary, outlier / shifted / masked value cases per row and
+per element, the saved statistics, the second grid-stride trip, stray writes, refusals and
+fall-backs — are in tests/test_transformer_rows_gpu.py (references: tests/rows_ref.py)."""
 
 import pytest
 import torch
