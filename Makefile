@@ -7,6 +7,7 @@ SRC := samplers_amd/csrc/sp_dps.hip samplers_amd/csrc/sp_blur.hip samplers_amd/c
        samplers_amd/csrc/sp_psf.hip samplers_amd/csrc/sp_phase.hip \
        samplers_amd/csrc/sp_psf_fft.hip samplers_amd/csrc/sp_radon.hip \
        samplers_amd/csrc/sp_svd_sep.hip samplers_amd/csrc/sp_hadamard.hip \
+       samplers_amd/csrc/sp_chanmix.hip \
        samplers_amd/csrc/sp_latent.hip samplers_amd/csrc/sp_cg.hip \
        samplers_amd/csrc/sp_groupnorm.hip samplers_amd/csrc/sp_conv.hip \
        samplers_amd/csrc/sp_wino.hip samplers_amd/csrc/sp_conv_thin.hip \

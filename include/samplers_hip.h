@@ -33,6 +33,10 @@
  *     PHASE: the kind's own launches read x, eps, y, g and write y, v, dx by scalar access (any
  *     width, any pads, 4-byte alignment); its workspace holds (re, im) pairs and must be 8-byte
  *     aligned.  Pass 2 over its v follows the rule above (n % 4 == 0 -> 16-byte aligned rows).
+ *     CHANNEL_MIX: its launches choose float4 access from height * width % 4 == 0 and then
+ *     REQUIRE 16-byte aligned rows of x and of y (every plane of a row then starts 16-byte
+ *     aligned); otherwise all its access is scalar and 4-byte alignment suffices.  Pass 2 over its v
+ *     follows the rule above.
  */
 #ifndef SAMPLERS_HIP_H
 #define SAMPLERS_HIP_H
@@ -126,7 +130,7 @@ enum {
                            The maps need a workspace: sp_op_apply_ws = A, sp_op_vjp_ws =
                            A^T, sp_op_pinv_ws = A^+ / A^+T, the fused DPS, PGDM, proximal
                            and DDRM passes as PSF_PERIODIC                           */
-    SP_OP_HADAMARD = 12 /* new: compressed sensing on a scrambled Walsh-Hadamard transform.  Per
+    SP_OP_HADAMARD = 12, /* new: compressed sensing on a scrambled Walsh-Hadamard transform.  Per
                            channel plane, with i = h*width + w and n_p = height*width = 2^k,
                            (A x)[c][r] = n_p^(-1/2) sum_i (-1)^popcount(j_r & i) d[i] x[c][i]:
                            j_r the r-th kept coefficient in ascending natural (Sylvester)
@@ -152,6 +156,25 @@ enum {
                            stage's tiles per plane); the q of sp_pgdm_prepare is y copied,
                            rows of m floats (sp_pgdm_residual_ws and sp_ddrm_step_ws read
                            it), sp_prox_prepare prepares nothing: the prox entries read y */
+    SP_OP_CHANNEL_MIX = 13 /* new: y = M x across the channel axis at every pixel, M a Cy x C
+                           matrix (colorization by mean or luma weights, a colour-correction or
+                           sensor-response matrix, spectral bands mixed down to RGB):
+                           y[i][h][w] = sum_c M[i][c] x[c][h][w].  channels = C, radius = Cy,
+                           factor = 0; 1 <= Cy <= C <= 8; height, width >= 1 with height * width
+                           < 2^31; n = C*height*width, m = Cy*height*width, y is (Cy, height,
+                           width); taps holds the six tables (below); keep_bits and word_rank
+                           NULL.  Block-diagonal over the pixels and the SVD of the operator is
+                           the SVD of M, so every pass is ONE launch with no halo and no workspace
+                           (csrc/sp_chanmix.hip): sp_op_apply / sp_op_adjoint (from M),
+                           sp_op_pinv_ws = A^+ / A^+T (from N), DPS pass 1, the PGDM pass 1 (it
+                           reads the observation rows themselves), the proximal map, the DiffPIR
+                           step and the DDRM step.  sp_rsq_partials is the tiles per sample:
+                           ceil(G / 256) with G = height*width / 4 groups of four pixels where
+                           height*width % 4 == 0, else G = height*width.  Every workspace size
+                           (sp_dps_workspace, sp_op_workspace, sp_prox_workspace,
+                           sp_prox_prepare_size, sp_ddrm_workspace) is 0 and every `work` and the
+                           q of the prox and DDRM entries may be NULL; sp_pgdm_prepare writes
+                           nothing and returns SP_OK, and sp_pgdm_residual_ws takes y as its q */
 };
 
 /* Forward-operator descriptor.  Device arrays are owned by the caller
@@ -224,7 +247,22 @@ typedef struct sp_op {
                                         elsewhere.  Computed in fp64 by the caller
                                         and rounded to fp32; the map is defined by
                                         these fp32 tables taken as exact, the library
-                                        does not read them on the host              */
+                                        does not read them on the host.  CHANNEL_MIX:
+                                        six row-major tables back to back, 2*C*Cy +
+                                        Cy*Cy + C*C + 2*Cy floats, with M = U S V^T the
+                                        SVD of the matrix: M[Cy][C]; N[C][Cy] = A^+ =
+                                        V diag(P) U^T; U[Cy][Cy], orthogonal, column j
+                                        the j-th left singular vector; V[C][C], full
+                                        orthogonal, column j the j-th right singular
+                                        vector by descending singular value, the
+                                        null-space completion after them; S[Cy]; P[Cy]
+                                        = 1 / S on the kept set, 0 elsewhere.  A and A^T
+                                        are evaluated from M, A^+ and A^+T from N, the
+                                        proximal map and the DDRM step from U, V, S, P.
+                                        Computed in fp64 by the caller and rounded to
+                                        fp32; the map is defined by these fp32 tables
+                                        taken as exact, the library does not read them
+                                        on the host                                  */
     int32_t radius;                  /* BLUR: 1..8.  PSF: 1..30.  PHASE: pad_h >= 0,
                                         zero rows added above and below.  PSF_FFT:
                                         1..min(height, width) - 1.  PSF_PERIODIC:
@@ -232,7 +270,8 @@ typedef struct sp_op {
                                         the taps per axis K, factor..min(height,
                                         width), K - factor even.  RADON: the
                                         number of angles, 1..512.  SVD_SEPARABLE: Hy,
-                                        the rows of y, 1..height                 */
+                                        the rows of y, 1..height.  CHANNEL_MIX: Cy, the
+                                        channels of y, 1..channels               */
     int32_t factor;                  /* SR, SR_PERIODIC: 2, 4 or 8.  PHASE: pad_w >= 0, zero
                                         columns added left and right.  PSF_FFT: the
                                         boundary: 0 reflect, 1 circular, 2 zeros (0
@@ -338,7 +377,11 @@ int sp_debug_selftest(sp_stream_t stream);
  * SVD_SEPARABLE: the 64 x 64 tiles of the observed grid per sample, channels * ceil(Hy / 64) *
  * ceil(Wy / 64) (csrc/sp_svd_sep.hip); rejected unless taps != NULL, 2 <= height, width <= 512,
  * 1 <= radius (Hy) <= height, 1 <= factor (Wy) <= width, n == channels*height*width,
- * m == channels*Hy*Wy and keep_bits and word_rank are NULL. */
+ * m == channels*Hy*Wy and keep_bits and word_rank are NULL.  CHANNEL_MIX: the tiles of 256 pixel
+ * groups per sample (csrc/sp_chanmix.hip; four pixels to a group where height*width % 4 == 0, else
+ * one); rejected unless taps != NULL, 1 <= radius (Cy) <= channels <= 8, factor == 0, height, width
+ * >= 1, height*width < 2^31, n == channels*height*width, m == radius*height*width and keep_bits and
+ * word_rank are NULL. */
 int64_t sp_rsq_partials(const sp_op* op);
 /* Floats of `work` that sp_dps_residual_ws / _sched_ws need for `batch` samples of `op`:
  * 0 for every kind but those below (one pass, no workspace), batch * m for PSF (its residual launch
@@ -506,6 +549,13 @@ int sp_op_vjp_ws(const sp_op* op, const float* x, const float* g, float* dx, int
  * launches' intermediate; two launches.  sp_pgdm_residual_ws is
  * v = grad_scale * T^-1[q - K * T(x0)] with T(X) = V_H^T X V_W on the observed grid and K = (P != 0),
  * i.e. grad_scale * (A^+ y - Pi x0), in four launches (the subtraction in the second one's epilogue).
+ * CHANNEL_MIX: one launch each and no workspace: sp_op_workspace is 0 and `work` may be NULL in
+ * sp_op_pinv_ws and sp_pgdm_residual_ws (for every other kind a NULL work is SP_EINVAL, as before).
+ * sp_op_pinv_ws is x[c] = sum_i N[c][i] y[i] per pixel (transpose = 1: y[i] = sum_c N[c][i] x[c]).
+ * sp_pgdm_prepare writes nothing and returns SP_OK (q must still be non-null): the residual launch
+ * reads the observation rows themselves, so the caller passes y as the q of sp_pgdm_residual_ws,
+ * rows of m floats; v = grad_scale * N (y - M x0) per pixel, nothing proportional to the batch is
+ * allocated or copied.
  * work and q must not alias any other argument. */
 int sp_op_pinv_ws(const sp_op* op, const float* y, float* x, int64_t batch, int32_t transpose,
                   float* work, sp_stream_t stream);
@@ -528,6 +578,8 @@ int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const
  *   SVD_SEPARABLE (A = U S V_obs^T)       Z = (S * T_y(y) + rho T(x0)) / (S^2 + rho) on the observed
  *                                         grid, T(x0) itself outside it (a select), z = T^-1 Z: exact
  *                                         for the full A, every component divided.
+ *   CHANNEL_MIX (M = U S V^T per pixel)   z = x0 + V diag(S / (S^2 + rho)) U^T r over all Cy singular
+ *                                         values, one launch that reads y (csrc/sp_chanmix.hip).
  * Every other kind: SP_EUNSUPPORTED (after the common argument checks, which answer SP_EINVAL).
  * The scalars are applied as reciprocals computed once per thread (1 / a, 1 / k, 1 / (1 + rho s^2),
  * 1 / (|M|^2 + rho)), as sp_dps_update does.  Plain stores, no atomics; every sample is computed

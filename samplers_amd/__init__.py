@@ -8,5 +8,18 @@ reference; the per-step arithmetic runs in hand-written HIP kernels
 
 __version__ = "0.1.0"
 
+__all__: list[str] = []  # `from samplers_amd import *` stays empty and imports nothing heavy
+
+
+def __getattr__(name: str):
+    # `samplers_amd.ChannelMixOperator` (also samplers_amd.operators.ChannelMixOperator, with the
+    # other operators): the operators import torch, so it resolves on first use
+    if name == "ChannelMixOperator":
+        from samplers_amd.operators.channel_mix import ChannelMixOperator
+
+        return ChannelMixOperator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 # MIOpen's find-db seed (samplers_amd/runtime.py) is merged lazily, before the first
 # convolution that falls back to MIOpen (none does in the priors' DPS / PSLD steps).

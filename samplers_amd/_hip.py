@@ -35,6 +35,9 @@ SP_OP_SVD_SEPARABLE = 11
 # compressed sensing on a scrambled Walsh-Hadamard transform, y = S H D x per plane (butterflies in
 # LDS): a partial isometry with every pass of SP_OP_SVD_SEPARABLE, y of (C, m / C)
 SP_OP_HADAMARD = 12
+# y = M x across the channel axis at every pixel (colorization, colour matrices): every pass one
+# launch without a workspace, y of (radius, H, W)
+SP_OP_CHANNEL_MIX = 13
 # sp_op_traits bits: what a kind does at the entry points (the library's table, not a list here)
 SP_TRAIT_UPDATE_READS_V, SP_TRAIT_DPS_WORKSPACE, SP_TRAIT_FUSED_LATENT = 1, 2, 4
 SP_TRAIT_LINEAR, SP_TRAIT_NEEDS_ATA_U, SP_TRAIT_PINV = 8, 16, 32

@@ -27,7 +27,7 @@ namespace sp {
 // (SP_TU << 16 | __LINE__; SP_TU numbers the source files: 0 = this header, 1 sp_dps, 2 sp_blur,
 // 3 sp_latent, 4 sp_groupnorm, 5 sp_conv, 6 sp_wino, 7 sp_conv_thin, 8 sp_conv_s2, 9 sp_upsample,
 // 10 sp_attention, 11 sp_gemm_x6, 12 sp_transformer, 13 sp_attention6, 14 sp_bf16_conv, 15 sp_sr, 16 sp_psf, 17 sp_phase,
-// 18 sp_psf_fft, 19 sp_radon, 20 sp_bf16_groupnorm, 21 sp_bf16_rows, 22 sp_bf16_attention, 23 sp_cg, 24 sp_svd_sep, 25 sp_hadamard; sp_fft.h and
+// 18 sp_psf_fft, 19 sp_radon, 20 sp_bf16_groupnorm, 21 sp_bf16_rows, 22 sp_bf16_attention, 23 sp_cg, 24 sp_svd_sep, 25 sp_hadamard, 26 sp_chanmix; sp_fft.h and
 // sp_bf16.h count under the file that includes them); the kernel then
 // goes on unchanged (a check never alters what a kernel reads or writes — the buffer range
 // checks of the release build stay as they are), and sp_debug_violations() reads the counts

@@ -634,12 +634,23 @@ static constexpr op_kind g_kinds[] = {
      .pgdm_residual = hadamard_pgdm_residual, .prox_workspace = hadamard_workspace,
      .prox = hadamard_prox, .diffpir_step = hadamard_prox,
      .ddrm_workspace = hadamard_workspace, .ddrm_step = hadamard_ddrm},
+    /* SP_OP_CHANNEL_MIX: a Cy x C matrix across the channels at every pixel: SR's one-launch
+       columns on the SVD of the matrix, and the pseudo-inverse columns without a workspace (the
+       PGDM launch reads y itself); PSLD as BLUR, through the maps and the cotangent */
+    {.valid = chanmix_valid, .partials = chanmix_partials, .dps_residual = chanmix_dps_residual,
+     .apply = chanmix_apply, .adjoint = chanmix_adjoint,
+     .psld_cotangent = elementwise_psld_cotangent,
+     .traits = SP_TRAIT_UPDATE_READS_V | SP_TRAIT_LINEAR | SP_TRAIT_NEEDS_ATA_U | SP_TRAIT_PINV,
+     .pinv_ws = chanmix_pinv, .pgdm_prepare = chanmix_pgdm_prepare,
+     .pgdm_residual = chanmix_pgdm_residual, .prox = chanmix_prox, .diffpir_step = chanmix_prox,
+     .ddrm_step = chanmix_ddrm},
 };
 constexpr int kKinds = sizeof(g_kinds) / sizeof(g_kinds[0]);
 static_assert(SP_OP_IDENTITY == 0 && SP_OP_INPAINT == 1 && SP_OP_BLUR == 2 && SP_OP_MASK == 3 &&
                   SP_OP_SR == 4 && SP_OP_PSF == 5 && SP_OP_PHASE == 6 && SP_OP_PSF_FFT == 7 &&
                   SP_OP_PSF_PERIODIC == 8 && SP_OP_RADON == 9 && SP_OP_SR_PERIODIC == 10 &&
-                  SP_OP_SVD_SEPARABLE == 11 && SP_OP_HADAMARD == 12 && kKinds == 13,
+                  SP_OP_SVD_SEPARABLE == 11 && SP_OP_HADAMARD == 12 && SP_OP_CHANNEL_MIX == 13 &&
+                  kKinds == 14,
               "g_kinds rows follow the sp_op kind numbering");
 
 const op_kind* kind_of(const sp_op* op) {
@@ -657,7 +668,7 @@ using namespace sp;
 
 extern "C" {
 
-int sp_version(void) { return 114; }
+int sp_version(void) { return 115; }
 
 int sp_debug_build(void) { return SP_DEBUG; }
 
@@ -926,12 +937,17 @@ int sp_op_adjoint(const sp_op* op, const float* y, float* x, int64_t batch, sp_s
     return k->adjoint(op, y, x, batch, static_cast<hipStream_t>(stream));
 }
 
+// a kind with pseudo-inverse passes and no workspace for them: `work` is not read
+static bool pinv_without_work(const op_kind* k) { return k->pinv_ws && !k->op_workspace; }
+
 int sp_op_pinv_ws(const sp_op* op, const float* y, float* x, int64_t batch, int32_t transpose,
                   float* work, sp_stream_t stream) {
-    if (!valid_op(op) || !y || !x || !work || batch <= 0 || batch > 65535 ||
+    if (!valid_op(op)) return SP_EINVAL;
+    const op_kind* k = kind_of(op);
+    // work may be null only for a kind whose pseudo-inverse needs none (sp_op_workspace is 0)
+    if (!y || !x || (!work && !pinv_without_work(k)) || batch <= 0 || batch > 65535 ||
         (transpose != 0 && transpose != 1))
         return SP_EINVAL;
-    const op_kind* k = kind_of(op);
     if (!k->pinv_ws) return SP_EUNSUPPORTED;
     return k->pinv_ws(op, y, x, batch, transpose, work, static_cast<hipStream_t>(stream));
 }
@@ -946,10 +962,11 @@ int sp_pgdm_prepare(const sp_op* op, const float* y, int64_t rows, float* q, sp_
 int sp_pgdm_residual_ws(const sp_op* op, const float* x, const float* eps, const float* q,
                         int64_t batch, int64_t y_div, const sp_dps_coefs* c, float* v_out,
                         float* work, sp_stream_t stream) {
-    if (!valid_op(op) || !x || !eps || !q || !c || !v_out || !work || batch <= 0 || y_div <= 0 ||
-        batch > 65535)
-        return SP_EINVAL;
+    if (!valid_op(op)) return SP_EINVAL;
     const op_kind* k = kind_of(op);
+    if (!x || !eps || !q || !c || !v_out || (!work && !pinv_without_work(k)) || batch <= 0 ||
+        y_div <= 0 || batch > 65535)
+        return SP_EINVAL;
     if (!k->pgdm_residual) return SP_EUNSUPPORTED;
     return k->pgdm_residual(op, x, eps, q, batch, y_div, *c, v_out, work,
                             static_cast<hipStream_t>(stream));

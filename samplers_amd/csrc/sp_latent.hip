@@ -336,7 +336,8 @@ int elementwise_psld_cotangent(const sp_op* op, const float* atr, const float* u
         case SP_OP_IDENTITY: if (v4) SP_CT(SP_OP_IDENTITY, 4); else SP_CT(SP_OP_IDENTITY, 1); break;
         case SP_OP_BLUR:
         case SP_OP_PSF:
-        case SP_OP_RADON: if (v4) SP_CT(SP_OP_BLUR, 4); else SP_CT(SP_OP_BLUR, 1); break;  // A^T A u given
+        case SP_OP_RADON:
+        case SP_OP_CHANNEL_MIX: if (v4) SP_CT(SP_OP_BLUR, 4); else SP_CT(SP_OP_BLUR, 1); break;  // A^T A u given
         default: if (v4) SP_CT(SP_OP_MASK, 4); else SP_CT(SP_OP_MASK, 1); break;
     }
 #undef SP_CT

@@ -193,5 +193,16 @@ pgdm_prepare_fn hadamard_pgdm_prepare;
 pgdm_residual_fn hadamard_pgdm_residual;
 prox_fn hadamard_prox;  // both forms: p.eps selects
 ddrm_fn hadamard_ddrm;
+// SP_OP_CHANNEL_MIX (sp_chanmix.hip: a small matrix across the channel axis at every pixel; every
+// pass one launch without a workspace, the PGDM pass reads y itself)
+valid_fn chanmix_valid;
+partials_fn chanmix_partials;
+dps_residual_fn chanmix_dps_residual;
+map_fn chanmix_apply, chanmix_adjoint;
+pinv_ws_fn chanmix_pinv;
+pgdm_prepare_fn chanmix_pgdm_prepare;
+pgdm_residual_fn chanmix_pgdm_residual;
+prox_fn chanmix_prox;  // both forms: p.eps selects
+ddrm_fn chanmix_ddrm;
 
 }  // namespace sp

@@ -1,5 +1,6 @@
 from .base import NonlinearOperator, Operator
 from .blur import GaussianBlurOperator
+from .channel_mix import ChannelMixOperator
 from .hadamard import HadamardOperator
 from .identity import IdentityOperator
 from .inpainting import (
@@ -47,6 +48,7 @@ __all__ = [
     "PeriodicBlurOperator",
     "SeparableSVDOperator",
     "HadamardOperator",
+    "ChannelMixOperator",
     "PhaseRetrievalOperator",
     "RadonOperator",
     "radon_table",

@@ -29,9 +29,10 @@ schedule asks for.  The class is decided by the one fp32 expression
 The fused path (``sp_ddrm_workspace`` is the probe) serves the identity, inpainting / mask,
 ×s average-pooling super-resolution, the periodic blur, the separable-SVD operator (any blur
 or filtered super-resolution of the form ``A_H X A_Wᵀ``) and the Walsh–Hadamard compressed-sensing
-operator (a partial isometry: one class for its whole kept set); any other ``SVDOperator`` without a
+operator (a partial isometry: one class for its whole kept set) and the channel-mixing operator
+(colorization: the SVD of its small matrix at every pixel); any other ``SVDOperator`` without a
 HIP descriptor takes ``ddrm_step_svd``, the same step in plain torch through its factors (so does
-the separable-SVD and Hadamard operators on host tensors); the rest
+the separable-SVD, Hadamard and channel-mixing operators on host tensors); the rest
 raise ``NotImplementedError``.  The noise model must be ``GaussianNoise`` unless ``noise_std`` is
 given.  The run starts from ``initial_sample`` rather than DDRM's spectral initialisation: at
 ``ᾱ_T ≈ 4e-5`` the two coincide.  Noise sources (``rng`` / ``seed`` / ``noise_fn``) are
@@ -59,7 +60,8 @@ from samplers_amd.samplers.utils.bridge_kernels import (DDRMCoefficients, ddrm_c
 Condition_co = TypeVar("Condition_co", covariant=True)
 
 SUPPORTED = ("IdentityOperator, InpaintingOperator (and subclasses), SuperResolutionOperator, "
-             "PeriodicBlurOperator, SeparableSVDOperator, HadamardOperator, or an SVDOperator without "
+             "PeriodicBlurOperator, SeparableSVDOperator, HadamardOperator, ChannelMixOperator, or an "
+             "SVDOperator without "
              "a HIP descriptor (GeneralSVDOperator)")
 
 

@@ -54,7 +54,8 @@ def prox_descriptor(operator) -> "_hip.SpOp":
             f"{type(operator).__name__} has no closed-form proximal map (apply_prox): DiffPIR "
             "supports IdentityOperator, InpaintingOperator (and subclasses), "
             "SuperResolutionOperator, PeriodicBlurOperator, "
-            "PeriodicSuperResolutionOperator, SeparableSVDOperator and HadamardOperator")
+            "PeriodicSuperResolutionOperator, SeparableSVDOperator, HadamardOperator and "
+            "ChannelMixOperator")
     return desc
 
 

@@ -189,7 +189,8 @@ class FusedDPSStep(FusedStep):
                 "supports IdentityOperator, InpaintingOperator (and subclasses), "
                 "GaussianBlurOperator, SuperResolutionOperator, PSFBlurOperator (and subclasses), "
                 "FFTPSFBlurOperator, PeriodicBlurOperator, PeriodicSuperResolutionOperator, "
-                "SeparableSVDOperator, HadamardOperator, RadonOperator and PhaseRetrievalOperator"
+                "SeparableSVDOperator, HadamardOperator, ChannelMixOperator, RadonOperator and "
+                "PhaseRetrievalOperator"
             )
         super().__init__(network, op, y_div, micro_batch, timer)
         self._bind_rows(observation_rows, "DPSSampler")
@@ -232,7 +233,10 @@ class FusedDPSStep(FusedStep):
         self.needs_v = bool(self.traits & _hip.SP_TRAIT_UPDATE_READS_V) or bool(reuse_v)
         # PGDM through the kind's own pseudo-inverse: Q = P FFT2(y), once (y is fixed across steps)
         if mode == "pgdm" and self.pinv:
-            self._prepare_q("sp_op_workspace", "sp_pgdm_prepare")
+            if int(self.lib.sp_op_workspace(desc, 1)) == 0:
+                self.q = self.y  # nothing to prepare: the launch reads the rows themselves
+            else:
+                self._prepare_q("sp_op_workspace", "sp_pgdm_prepare")
 
     def coefficients(self, t: int, t_prev: int, s: int) -> _hip.SpDpsCoefs:
         acp = host_alphas_cumprod(self.network)

@@ -12,6 +12,8 @@ is ``sp_pgdm_residual_ws``, v = −2 (A⁺y − A⁺A x0), over Q = P ⊙ FFT2(y
 ``SeparableSVDOperator`` (v = −2 (A⁺y − Π x0) through the SVDs of its two factors, q = P ⊙ U_Hᵀ y U_W;
 on host tensors ``HostPGDMStep``, the reference's loop body in plain torch through its host maps).
 ``HadamardOperator`` (A⁺ = Aᵀ) likewise: v = −2 Aᵀ(y − A x0), q holding y itself.
+``ChannelMixOperator``: v = −2 A⁺(y − A x0) per pixel in one launch that reads the observation rows
+themselves (no q, no workspace).
 Operators without ``apply_pseudo_inverse`` raise ``NotImplementedError`` as in
 the reference (``pgdm.py:56-66``).
 """
