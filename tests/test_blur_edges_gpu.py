@@ -32,6 +32,7 @@ import torch
 
 import blur_ref as br
 import exact_cases as ec
+from kind_harness import stream as _stream
 from oracle import closed_form
 from samplers_amd import _hip
 from samplers_amd.operators import GaussianBlurOperator
@@ -52,10 +53,6 @@ NEAR = ([("tile", r, br.tile_cases(r)[1][0]) for r in range(1, 9)]
         + [("reg", r, (1, 64, 256)) for r in range(1, 5)]
         + [("dma", r, (2, 96, 256)) for r in range(1, 5)])
 NEAR_IDS = [f"{k}-R{r}-{sid(s)}" for k, r, s in NEAR]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _call(name, *args):

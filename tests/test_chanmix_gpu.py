@@ -15,22 +15,17 @@ reference loop's distance to its fp64 run); PSLD 1e-4 (tests/test_superres_gpu.p
 
 Largest errors measured on an MI355X are recorded in README.md ("Channel-mixing operator")."""
 
-import math
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
 import chanmix_ref as cr
 import ddrm_ref as dr
-import prox_ref as pr
 import stand_ins as si
-from oracle import dps_loop
-from oracle.latent_loops import pgdm_reference, psld_reference
+from kind_harness import (DDRM, DEBUG_SWEEP_CHILD, DPS, PROX, KindDevice, acp as _acp,
+                          check_fused_path_and_reproduce, check_guards, check_trajectory, counting_net,
+                          f32 as _f32, guarded, rounding_check as _check, run_debug_child, stream as _stream)
+from oracle.latent_loops import psld_reference
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise
@@ -38,168 +33,62 @@ from samplers_amd.operators import ChannelMixOperator, IdentityOperator
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
-OFFSET = 5  # sample_offset of the Philox calls
 CASE_IDS = [c[0] for c in cr.CASES]
-DPS = dict(a=0.3, k=math.sqrt(1 - 0.09), gs=400.0)
-PROX = dict(a=0.8, k=0.6, rho=0.37, a_prev=0.9, c_eps=0.3, c_xi=0.2)
-DDRM = {"big": dr.make_coefs(3.0, 0.05, 0.85, 1.0), "blend": dr.make_coefs(0.5, 0.05, 0.5, 0.5),
-        "small": dr.make_coefs(0.041, 0.05, 0.85, 1.0), "sig_y=0": dr.make_coefs(0.23, 0.0, 0.85, 1.0),
-        "sig_prev=0": dr.make_coefs(0.0, 0.05, 0.85, 1.0)}
 FORMS = [(i, f) for i in range(len(cr.CASES)) for f in cr.FORMS]
 FORM_IDS = [f"{CASE_IDS[i]}-b{f[0]}-d{f[1]}" for i, f in FORMS]
-TRAITS = (_hip.SP_TRAIT_LINEAR | _hip.SP_TRAIT_UPDATE_READS_V | _hip.SP_TRAIT_NEEDS_ATA_U
-          | _hip.SP_TRAIT_PINV)
 
 
-def _f32(d):
-    return {k: float(np.float32(v)) for k, v in d.items()}
+# --- a descriptor on the device -----------------------------------------------------------------------------
+class Dev(KindDevice):
+    """The tables on the device and the descriptor.  The kind takes no workspace (every `work` is
+    NULL), its maps run through the plain entry points, and every pass reads the observation rows."""
 
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-# --- a descriptor on the device and the raw calls ---------------------------------------------------------
-class Dev:
-    """The tables on the device, the descriptor and every entry point into guarded buffers."""
+    TRAITS = _hip.SP_TRAIT_LINEAR | _hip.SP_TRAIT_UPDATE_READS_V | _hip.SP_TRAIT_NEEDS_ATA_U | _hip.SP_TRAIT_PINV
+    WORKSPACE_FORMS = False
 
     def __init__(self, shape, tab32, device, name=""):
-        self.lib = _hip.load_library()
-        self.name, (self.C, self.Cy, self.H, self.W) = name, shape
-        self.device = device
+        self.C, self.Cy, self.H, self.W = self.shape = shape
         self.hw = self.H * self.W
-        self.n, self.m = self.C * self.hw, self.Cy * self.hw
         self.taps = torch.from_numpy(cr.flat_tables(tab32)).to(device)
         assert self.taps.numel() == 2 * self.C * self.Cy + self.Cy ** 2 + self.C ** 2 + 2 * self.Cy
         s = _hip.SpOp()
         s.kind, s.channels, s.height, s.width = _hip.SP_OP_CHANNEL_MIX, self.C, self.H, self.W
-        s.n, s.m, s.radius, s.factor = self.n, self.m, self.Cy, 0
+        s.n, s.m, s.radius, s.factor = self.C * self.hw, self.Cy * self.hw, self.Cy, 0
         s.taps = self.taps.data_ptr()
-        self.desc = s
-        assert self.lib.sp_op_traits(s) == TRAITS
+        super().__init__(device, s, (self.C, self.H, self.W), (self.Cy, self.H, self.W), name)
         for size in (self.lib.sp_op_workspace, self.lib.sp_dps_workspace, self.lib.sp_prox_workspace,
                      self.lib.sp_ddrm_workspace, self.lib.sp_prox_prepare_size):
-            assert size(s, 4) == 0  # no workspace anywhere: every `work` below is NULL
-        self.P = int(self.lib.sp_rsq_partials(s))
-        assert self.P == cr.partials(shape)
-        self.xs, self.ys = (self.C, self.H, self.W), (self.Cy, self.H, self.W)
+            assert size(s, 4) == 0
 
-    def guarded(self, floats):
-        """`floats` NaNs between two guard bands of 16 NaNs; (whole, view)."""
-        whole = torch.full((floats + 32,), float("nan"), device=self.device)
-        return whole, whole[16:16 + floats]
+    def check_workspace(self, floats, batch):
+        assert floats == 0
 
-    def _run(self, out_shape, call):
-        floats = int(np.prod(out_shape))
-        whole, out = self.guarded(floats)
-        out = out.view(out_shape)
-        _hip.check(call(out), "channel-mix entry")
-        assert torch.isnan(whole[:16]).all() and torch.isnan(whole[16 + floats:]).all()
-        assert torch.isfinite(out).all()
-        return out
-
-    def apply(self, x):
-        b = x.shape[0]
-        return self._run((b, *self.ys), lambda o: self.lib.sp_op_apply(self.desc, x.data_ptr(), o.data_ptr(), b,
-                                                                      _stream()))
-
-    def adjoint(self, y):
-        b = y.shape[0]
-        return self._run((b, *self.xs), lambda o: self.lib.sp_op_adjoint(self.desc, y.data_ptr(), o.data_ptr(), b,
-                                                                        _stream()))
-
-    def pinv(self, t, transpose=0):
-        b = t.shape[0]
-        return self._run((b, *(self.ys if transpose else self.xs)),
-                         lambda o: self.lib.sp_op_pinv_ws(self.desc, t.data_ptr(), o.data_ptr(), b, transpose, None,
-                                                          _stream()))
-
-    def dps(self, x, eps, y, ydiv, c, sched=False):
-        b = x.shape[0]
-        pwhole, part = self.guarded(b * self.P)
-        coefs = _hip.SpDpsCoefs(c["a"], c["k"], c["gs"], 0.9, 0.2, 0.1, 0.05, 1e-9)
-
-        def call(o):
-            if not sched:
-                return self.lib.sp_dps_residual(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b, ydiv,
-                                                coefs, o.data_ptr(), part.data_ptr(), _stream())
-            recs = (_hip.SpStepRec * 2)()
-            recs[0].c, recs[0].step, recs[0].t = _hip.SpDpsCoefs(0.9, 0.4, 7.0, 0.1, 0.9, 0.6, 0.5, 1e-3), 99, 1
-            recs[1].c, recs[1].step, recs[1].t = coefs, 3, 5
-            self._sched = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(self.device)
-            self._cursor = torch.ones(1, dtype=torch.int32, device=self.device)
-            return self.lib.sp_dps_residual_sched(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b, ydiv,
-                                                  self._sched.data_ptr(), self._cursor.data_ptr(), o.data_ptr(),
-                                                  part.data_ptr(), _stream())
-
-        v = self._run((b, *self.xs), call)
-        assert torch.isnan(pwhole[:16]).all() and torch.isnan(pwhole[16 + b * self.P:]).all()
-        assert torch.isfinite(part).all()
-        return v, part.view(b, self.P)
+    def partials(self):
+        return cr.partials(self.shape)
 
     def pgdm(self, x, eps, y, ydiv, c):
         """The observation rows themselves are the q of the pass; sp_pgdm_prepare writes nothing."""
-        b = x.shape[0]
-        qwhole, q = self.guarded(4)
+        qwhole, q = guarded(4, self.device)
         assert self.lib.sp_pgdm_prepare(self.desc, y.data_ptr(), y.shape[0], q.data_ptr(), _stream()) == 0
-        coefs = _hip.SpDpsCoefs(c["a"], c["k"], c["gs"], 0.9, 0.2, 0.1, 0.05, 1e-9)
-        out = self._run((b, *self.xs), lambda o: self.lib.sp_pgdm_residual_ws(
-            self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b, ydiv, coefs, o.data_ptr(), None, _stream()))
+        out = super().pgdm(x, eps, y, ydiv, c)
         assert torch.isnan(qwhole).all()
         return out
 
     def prox(self, x0, y, ydiv, rho):
-        b = x0.shape[0]
         assert self.lib.sp_prox_prepare(self.desc, y.data_ptr(), y.shape[0], None, _stream()) == 0
-        return self._run((b, *self.xs), lambda o: self.lib.sp_op_prox_ws(
-            self.desc, x0.data_ptr(), y.data_ptr(), None, b, ydiv, rho, o.data_ptr(), None, _stream()))
+        return super().prox(x0, y, ydiv, rho)
 
     def prox_cg(self, x0, y, ydiv, rho, iters=64, tol=1e-6):
         b = x0.shape[0]
         floats = int(self.lib.sp_prox_cg_workspace(self.desc, b, 0))
         assert floats > 0
-        wwhole, work = self.guarded(floats)
+        wwhole, work = guarded(floats, self.device)
         it = torch.full((b,), -1, dtype=torch.int32, device=self.device)
-        out = self._run((b, *self.xs), lambda o: self.lib.sp_op_prox_cg_ws(
+        out = self._run(self.lib.sp_op_workspace, b, (b, *self.xs), lambda o, w: self.lib.sp_op_prox_cg_ws(
             self.desc, x0.data_ptr(), y.data_ptr(), b, ydiv, rho, iters, tol, o.data_ptr(), it.data_ptr(),
             work.data_ptr(), _stream()))
-        assert torch.isnan(wwhole[:16]).all() and torch.isnan(wwhole[16 + floats:]).all()
+        check_guards(wwhole, floats)
         return out, it
-
-    def _step(self, entry, x, eps, y, xi, ydiv, coefs, alias, step):
-        b = x.shape[0]
-        src = x.clone() if alias else x
-
-        def call(o):
-            dst = src if alias else o
-            rc = entry(self.desc, src.data_ptr(), eps.data_ptr(), y.data_ptr(), None,
-                       None if xi is None else xi.data_ptr(), 77, step, OFFSET, b, ydiv, coefs, dst.data_ptr(),
-                       None, _stream())
-            if alias:
-                o.copy_(src)
-            return rc
-
-        return self._run((b, *self.xs), call)
-
-    def diffpir(self, x, eps, y, xi, ydiv, c, alias=False, step=3):
-        coefs = _hip.SpProxCoefs(c["a"], c["k"], c["rho"], c["a_prev"], c["c_eps"], c["c_xi"])
-        return self._step(self.lib.sp_diffpir_step_ws, x, eps, y, xi, ydiv, coefs, alias, step)
-
-    def ddrm(self, x, eps, y, xi, ydiv, c, alias=False, step=3):
-        coefs = _hip.SpDdrmCoefs(*[c[k] for k in dr.KEYS])
-        return self._step(self.lib.sp_ddrm_step_ws, x, eps, y, xi, ydiv, coefs, alias, step)
-
-    def randn(self, b, step=3):
-        out = torch.empty(b, *self.xs, device=self.device)
-        _hip.check(self.lib.sp_randn(out.data_ptr(), b, self.n, 77, step, OFFSET, _stream()), "sp_randn")
-        return out
-
-    def x0(self, x, eps, a, k):
-        out = torch.empty_like(x)
-        _hip.check(self.lib.sp_predict_x0(x.data_ptr(), eps.data_ptr(), x.numel(), a, k, out.data_ptr(),
-                                          _stream()), "sp_predict_x0")
-        return out
 
 
 def _dev(i, device):
@@ -219,16 +108,6 @@ def _randn_case(i):
         x, eps, xi = (torch.randn(4, c, h, w, generator=g) for _ in range(3))
         _DATA[i] = (x, eps, xi, torch.randn(2, cy, h, w, generator=g))
     return _DATA[i]
-
-
-def _check(got, ref64, env, n_r, what, record=None):
-    """max over the elements of |got − ref64| / (n_r · 2⁻²⁴ · E) ≤ 1."""
-    ratio = float(((got.detach().cpu().double() - ref64).abs() / (n_r * cr.U24 * env)).max())
-    print(f"{what}: worst |err| / (n_r 2^-24 E) = {ratio:.3g} (n_r = {n_r})")
-    if record is not None:
-        record(f"{what}_err_over_bound", ratio, 1.0, n_r=n_r)
-    assert ratio <= 1.0, (what, ratio)
-    return ratio
 
 
 def test_tile_counts():
@@ -481,83 +360,13 @@ def _traj(weights, cuda):
     return op, _tables_of(host), y, InverseProblem(op, y.to(cuda), GaussianNoise(SIGMA).to(cuda))
 
 
-def _acp(dt=torch.float32):
-    return torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).to(dt)
-
-
-def _net(cuda):
-    net = si.make_samplers_amd_net("conv", 3, 0.1, device=cuda)
-    grads, inner = [], net.forward
-
-    def forward(x, t):
-        e = inner(x, t)
-        grads.append(bool(e.requires_grad) or torch.is_grad_enabled())
-        return e
-
-    net.forward = forward
-    return net, grads
-
-
-def _bound_check(out, run, what, record):
-    ref32 = run(torch.float32)
-    cond = si.relative_error(run(torch.float64), ref32)
-    bound = max(1e-4, 20 * cond)
-    err = si.relative_error(out.reshape(ref32.shape).cpu(), ref32)
-    print(f"{what}: rel l2 {err:.3g}, fp32 reference to fp64 {cond:.3g}, bound {bound:.3g}")
-    record(f"{what}_rel_l2", err, bound, fp32_to_fp64=cond)
-    assert err < bound
-
-
 @pytest.mark.parametrize("recon", [1, 2])
 @pytest.mark.parametrize("weights", ["mean", "luma"])
 @pytest.mark.parametrize("sampler", ["dps", "pgdm", "diffpir", "ddrm"])
 def test_trajectory_matches_the_reference_loop(cuda, parity_record, sampler, weights, recon):
-    from samplers_amd.samplers import DDRMSampler, DiffPIRSampler, DPSSampler, PGDMSampler
-
     op, tab, y, prob = _traj(weights, cuda)
-    net, grads = _net(cuda)
-    init, steps = si.replay_noise(17, (B * recon, *SHAPE), N)
-    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
-    ts = si.leading_timesteps_ascending(N).tolist()
-    yr = y.repeat_interleave(recon, dim=0)
-    kw = dict(num_sampling_steps=N, num_reconstructions=recon, noise_fn=fn,
-              micro_batch=2 if recon == 2 else None)
-
-    def loop(dt):
-        core, S = si.EpsCore("conv", 3, 0.1).to(dt), cr.Mix(FULL, tab, dtype=dt)
-        eps_fn = lambda x, tt: core(x, tt)  # noqa: E731
-        noise = lambda i: steps[i].to(dt)  # noqa: E731
-        if sampler == "dps":
-            return dps_loop.dps_reference(eps_fn, _acp(dt), ts, S.apply, dps_loop.gaussian_log_prob(SIGMA),
-                                          yr.to(dt), init.to(dt), noise, gamma=1e-2, eta=1.0)
-        if sampler == "pgdm":
-            return pgdm_reference(eps_fn, _acp(dt), ts, S.apply, S.pinv, yr.to(dt), init.to(dt), noise,
-                                  guidance_weight=0.05, eta=1.0)
-        if sampler == "diffpir":
-            return pr.diffpir_reference(eps_fn, _acp(dt), ts, S.apply, lambda x0, yy, rho: S.prox(x0, yy, float(rho)),
-                                        yr.to(dt), init.to(dt), noise, sigma=SIGMA)
-        step = lambda x, e, yy, xi, c: S.ddrm(x, e, yy, xi, dr.round32(c) if dt == torch.float32 else c)  # noqa: E731
-        return dr.ddrm_reference(eps_fn, _acp(dt), ts, step, yr.to(dt), init.to(dt), noise, sigma_y=SIGMA)
-
-    if sampler == "dps":
-        smp = DPSSampler(net)
-        out = smp(prob, gamma=1e-2, eta=1.0, **kw)
-    elif sampler == "pgdm":
-        smp = PGDMSampler(net)
-        out = smp(prob, guidance_weight=0.05, **kw)
-    elif sampler == "diffpir":
-        smp = DiffPIRSampler(net)
-        out = smp(prob, **kw)
-        assert not smp.last_step.cg and not smp.last_step.host
-    else:
-        smp = DDRMSampler(net)
-        out = smp(prob, **kw)
-        assert smp.last_step.fused
-    if sampler in ("diffpir", "ddrm"):
-        assert smp.last_step.desc.kind == _hip.SP_OP_CHANNEL_MIX  # the HIP path ran
-        assert len(grads) >= 2 and not any(grads)  # no network call builds an autograd graph
-    assert tuple(out.shape) == ((B, *SHAPE) if recon == 1 else (B, recon, *SHAPE))
-    _bound_check(out, loop, f"{sampler}_{weights}_R{recon}", parity_record)
+    check_trajectory(cuda, parity_record, sampler, _hip.SP_OP_CHANNEL_MIX, prob, y,
+                     lambda dt: cr.Mix(FULL, tab, dtype=dt), SHAPE, N, SIGMA, recon, f"{sampler}_{weights}_R{recon}")
 
 
 def test_psld_matches_the_reference_loop(cuda, parity_record):
@@ -583,32 +392,11 @@ def test_psld_matches_the_reference_loop(cuda, parity_record):
 
 
 def test_samplers_take_the_fused_path_and_reproduce(cuda):
-    from samplers_amd.samplers import DDRMSampler, DiffPIRSampler, DPSSampler, PGDMSampler
-    from samplers_amd.samplers.ddrm import FusedDDRMStep
-    from samplers_amd.samplers.diffpir import FusedDiffPIRStep
-    from samplers_amd.samplers.dps import FusedDPSStep, make_dps_step
-
     op, _, y, prob = _traj("mean", cuda)
-    net, _ = _net(cuda)
-    rows = y.to(cuda)
-    step = FusedDDRMStep(net, prob, rows, 1)
-    assert step.fused and step.q is None and step.desc.kind == _hip.SP_OP_CHANNEL_MIX
-    for mode in ("closed_form", "auto"):
-        st = FusedDiffPIRStep(net, prob, rows, 1, prox=mode)
-        assert not st.cg and st.q is None and st.desc.kind == _hip.SP_OP_CHANNEL_MIX
-    assert FusedDiffPIRStep(net, prob, rows, 1, prox="cg").cg
-    for mode in ("dps", "pgdm"):  # DPS and PGDM: the fused step on the kind's descriptor
-        st = make_dps_step(net, prob, rows, 1, mode=mode)
-        assert isinstance(st, FusedDPSStep) and st.desc.kind == _hip.SP_OP_CHANNEL_MIX and st.needs_v
-        # PGDM reads the observation rows themselves: no copy of y
-        assert st.q is None if mode == "dps" else st.q.data_ptr() == st.y.data_ptr()
-    for cls in (DPSSampler, PGDMSampler, DDRMSampler, DiffPIRSampler):
-        one = cls(net)(prob, num_sampling_steps=N, seed=1234)
-        assert torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1234), one) and torch.isfinite(one).all()
-        assert not torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1235), one)
-        assert torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1234, micro_batch=1), one)
-    out = DiffPIRSampler(net)(prob, num_sampling_steps=N, seed=3, prox="cg", cg_iterations=8)
-    assert torch.isfinite(out).all() and tuple(out.shape) == (B, *SHAPE)
+    net, _ = counting_net("conv", 3, 0.1, cuda)
+    steps = check_fused_path_and_reproduce(net, prob, y.to(cuda), _hip.SP_OP_CHANNEL_MIX, N, expect_q=False)
+    assert steps["closed_form"].q is None and steps["auto"].q is None
+    assert steps["pgdm"].q.data_ptr() == steps["pgdm"].y.data_ptr()  # the observation rows themselves: no copy of y
 
 
 # --- the bounds-checked library ------------------------------------------------------------------------------
@@ -634,27 +422,10 @@ def debug_sweep(device):
         assert nv == 0, (name, nv, site)
 
 
-DEBUG_CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + "/tests")
-from samplers_amd import _hip
-assert _hip.load_library().sp_debug_build() == 1, "not the debug library"
-import test_chanmix_gpu as T
-_hip.debug_violations()  # clear
-T.debug_sweep(torch.device("cuda:0"))
-print("debug build: clean", flush=True)
-"""
+DEBUG_CHILD = DEBUG_SWEEP_CHILD("test_chanmix_gpu")
 
 
 def test_debug_build_has_no_violations(cuda):
     """The kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh child
     process (a process holds one library), over every shape of this file."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -25,10 +25,6 @@ max(1e-4, 20 x the fp32 reference loop's distance to its fp64 run).
 Measured on an MI355X: see README.md "DDRM" (parity_record has every figure)."""
 
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
@@ -37,6 +33,7 @@ import ddrm_ref as dr
 import periodic_ops as po
 import stand_ins as si
 from exact_cases import Guarded, assert_bitwise
+from kind_harness import DEBUG_SWEEP_CHILD, run_debug_child, stream as _stream
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise
@@ -46,7 +43,6 @@ from samplers_amd.operators.blur import gaussian_taps
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 U = 2.0 ** -24
 BATCHES = [(3, 3), (4, 2)]  # (batch, y_div)
 SEED, STEP, OFFSET = 11, 5, 7
@@ -144,10 +140,6 @@ def _case(i, device):
     if i not in _CASES:
         _CASES[i] = Case(CASES[i], device)
     return _CASES[i]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _prepare(lib, c, y):
@@ -523,27 +515,10 @@ def debug_sweep(device):
         assert nv == 0, (IDS[i], nv, site)
 
 
-DEBUG_CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + "/tests")
-from samplers_amd import _hip
-assert _hip.load_library().sp_debug_build() == 1, "not the debug library"
-import test_ddrm_gpu as T
-_hip.debug_violations()  # clear
-T.debug_sweep(torch.device("cuda:0"))
-print("debug build: clean", flush=True)
-"""
+DEBUG_CHILD = DEBUG_SWEEP_CHILD("test_ddrm_gpu")
 
 
 def test_debug_build_has_no_violations(cuda):
     """The new kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh
     child process (a process holds one library), over every shape of this file."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -14,16 +14,11 @@ the final predictions.  No invariant may be violated.
 
 from __future__ import annotations
 
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import pytest
 
-pytestmark = pytest.mark.gpu
+from kind_harness import run_debug_child
 
-ROOT = Path(__file__).resolve().parents[1]
+pytestmark = pytest.mark.gpu
 
 CHILD = r"""
 import sys, torch
@@ -88,16 +83,7 @@ print("debug build: clean", flush=True)
 
 @pytest.mark.timeout(600)
 def test_debug_build_counts_violations_and_the_workloads_have_none(cuda):
-    from samplers_amd import _hip
-
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", CHILD, str(ROOT)], env=env, capture_output=True,
-                         text=True, timeout=540)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(CHILD, timeout=540)
 
 
 def test_release_build_reports_no_checks(cuda):

@@ -13,6 +13,7 @@ import torch
 
 import prox_ref as pr
 import stand_ins as si
+from kind_harness import make_descriptor as make
 from samplers_amd import _hip, operators as ops
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise, PoissonNoise
@@ -22,13 +23,6 @@ from samplers_amd.samplers.utils.bridge_kernels import diffpir_coefficients
 OK, EINVAL, EUNSUPPORTED = 0, -1, -3
 _buf = (ctypes.c_float * 64)()
 PTR = ctypes.addressof(_buf)  # a non-null dummy pointer: nothing here dereferences it
-
-
-def make(kind, n, m, c=0, h=0, w=0, radius=0, factor=0, taps=None, keep=None, rank=None):
-    d = _hip.SpOp()
-    d.kind, d.n, d.m, d.channels, d.height, d.width = kind, n, m, c, h, w
-    d.radius, d.factor, d.taps, d.keep_bits, d.word_rank = radius, factor, taps, keep, rank
-    return d
 
 
 def plane(kind, c, h, w, **kw):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from kind_harness import stream as _stream
 from oracle import blur as oblur
 from oracle import closed_form
 from samplers_amd import _hip
@@ -26,10 +27,6 @@ pytestmark = pytest.mark.gpu
 
 SHAPE, B = (3, 256, 256), 64
 N = math.prod(SHAPE)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def test_inpaint_operator_full_size_bit_exact(cuda):

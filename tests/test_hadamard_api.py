@@ -10,14 +10,10 @@ import numpy as np
 import pytest
 import torch
 
-import ddrm_ref as dr
 import hadamard_ref as hr
-import stand_ins as si
+from kind_harness import host_ddrm_check, host_diffpir_check, host_pgdm_check, host_refusals
 from samplers_amd import _hip
-from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.noise import GaussianNoise
 from samplers_amd.operators import HadamardOperator, SVDOperator
-from samplers_amd.samplers import DDRMSampler
 
 KIND, EINVAL, EUNSUPPORTED = 12, -1, -3
 _buf = (ctypes.c_float * 64)()
@@ -213,107 +209,22 @@ def _host_problem():
     return shape, sigma, op, (op.keep.numpy(), op.signs.numpy()), y
 
 
-def _loops(run):
-    """(fp32 reference loop, max(1e-4, 20 x its distance to the fp64 run))."""
-    ref32 = run(torch.float32)
-    return ref32, max(1e-4, 20 * si.relative_error(run(torch.float64), ref32))
-
-
-def _acp(dt):
-    return torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).to(dt)
-
-
 @pytest.mark.parametrize("recon", [1, 2])
 def test_host_ddrm_sampler_is_the_plain_loop(recon):
-    (shape, sigma, op, (keep, sg), y), N, B = _host_problem(), 6, 2
-    net = si.make_samplers_amd_net("conv", 1, 0.1)
-    calls, inner = [], net.forward
-
-    def forward(x, tt):
-        calls.append(torch.is_grad_enabled())
-        return inner(x, tt)
-
-    net.forward = forward
-    init, steps = si.replay_noise(21, (B * recon, *shape), N)
-    fn = lambda kind, i, sh: init.clone() if kind == "init" else steps[i]  # noqa: E731
-    smp = DDRMSampler(net)
-    out = smp(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=N, num_reconstructions=recon,
-              noise_fn=fn, micro_batch=2 if recon == 2 else None)
-    assert not smp.last_step.fused  # ddrm_step_svd through the host maps
-    assert tuple(out.shape) == ((B, *shape) if recon == 1 else (B, recon, *shape))
-    assert len(calls) >= N - 1 and not any(calls)  # every network call under no_grad
-    core, S = si.EpsCore("conv", 1, 0.1).double(), hr.Had(shape, keep, sg)
-    ref = dr.ddrm_reference(lambda x, tt: core(x, tt), _acp(torch.float64), si.leading_timesteps_ascending(N).tolist(),
-                            lambda x, e, yy, xi, c: S.ddrm(x, e, yy, xi, c),
-                            y.repeat_interleave(recon, dim=0).double(), init.double(),
-                            lambda i: steps[i].double(), sigma_y=sigma)
-    err = si.relative_error(out.reshape(ref.shape), ref)
-    print(f"host DDRM R={recon}: rel l2 {err:.3g}")
-    assert err <= 1e-4  # fp32 plain torch against the fp64 loop over N - 2 steps
-    # DPS has no host form: its fused step needs a device
-    from samplers_amd.samplers import DPSSampler
-    with pytest.raises(_hip.HipLibraryError):
-        DPSSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=4)
-    with pytest.raises((ValueError, _hip.HipLibraryError)):  # the host path draws no Philox noise
-        DDRMSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=4, seed=1)
+    shape, sigma, op, (keep, sg), y = _host_problem()
+    host_ddrm_check(op, hr.Had(shape, keep, sg), y, shape, sigma, recon)
+    host_refusals(op, y, shape, sigma)
 
 
 @pytest.mark.parametrize("recon", [1, 2])
 def test_host_pgdm_sampler_is_the_plain_loop(recon):
-    from oracle.latent_loops import pgdm_reference
-    from samplers_amd.samplers import PGDMSampler
-
-    (shape, sigma, op, (keep, sg), y), N, B = _host_problem(), 6, 2
-    net = si.make_samplers_amd_net("conv", 1, 0.1)
-    init, steps = si.replay_noise(21, (B * recon, *shape), N)
-    fn = lambda kind, i, sh: init.clone() if kind == "init" else steps[i]  # noqa: E731
-    out = PGDMSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=N,
-                           num_reconstructions=recon, guidance_weight=0.05, noise_fn=fn,
-                           micro_batch=2 if recon == 2 else None)
-    assert tuple(out.shape) == ((B, *shape) if recon == 1 else (B, recon, *shape))
-
-    def run(dt):
-        core, S = si.EpsCore("conv", 1, 0.1).to(dt), hr.Had(shape, keep, sg, dtype=dt)
-        return pgdm_reference(lambda x, tt: core(x, tt), _acp(dt), si.leading_timesteps_ascending(N).tolist(),
-                              S.apply, S.pinv, y.repeat_interleave(recon, dim=0).to(dt), init.to(dt),
-                              lambda i: steps[i].to(dt), guidance_weight=0.05, eta=1.0)
-
-    ref, bound = _loops(run)
-    err = si.relative_error(out.reshape(ref.shape), ref)
-    print(f"host PGDM R={recon}: rel l2 {err:.3g} bound {bound:.3g}")
-    assert err <= bound
+    shape, sigma, op, (keep, sg), y = _host_problem()
+    host_pgdm_check(op, lambda dt: hr.Had(shape, keep, sg, dtype=dt), y, shape, sigma, recon)
 
 
 @pytest.mark.parametrize("prox", ["cg", "closed_form", "auto"])
 def test_host_diffpir_sampler_is_the_plain_loop(prox):
-    import prox_ref as pr
-    from samplers_amd.samplers import DiffPIRSampler
-
-    (shape, sigma, op, (keep, sg), y), N, B, K, tol = _host_problem(), 6, 2, 16, 1e-6
-    net = si.make_samplers_amd_net("conv", 1, 0.1)
-    calls, inner = [], net.forward
-
-    def forward(x, tt):
-        calls.append(torch.is_grad_enabled())
-        return inner(x, tt)
-
-    net.forward = forward
-    init, steps = si.replay_noise(21, (B, *shape), N)
-    fn = lambda kind, i, sh: init.clone() if kind == "init" else steps[i]  # noqa: E731
-    sampler = DiffPIRSampler(net)
-    out = sampler(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=N, noise_fn=fn, prox=prox,
-                  cg_iterations=K, cg_tol=tol)
-    assert sampler.last_step.host and len(calls) >= N - 1 and not any(calls)  # every network call under no_grad
+    shape, sigma, op, (keep, sg), y = _host_problem()
+    sampler = host_diffpir_check(op, lambda dt: hr.Had(shape, keep, sg, dtype=dt), y, shape, sigma, prox, tol=1e-6)
     if prox == "cg":  # A Aᵀ = I: the recurrence stops within two iterations, on the closed form's point
-        assert tuple(sampler.last_step.iterations.shape) == (N - 2, B) and int(sampler.last_step.iterations.max()) <= 2
-
-    def run(dt):
-        core, S = si.EpsCore("conv", 1, 0.1).to(dt), hr.Had(shape, keep, sg, dtype=dt)
-        return pr.diffpir_reference(lambda x, tt: core(x, tt), _acp(dt), si.leading_timesteps_ascending(N).tolist(),
-                                    S.apply, lambda x0, yy, rho: S.prox(x0, yy, float(rho)), y.to(dt), init.to(dt),
-                                    lambda i: steps[i].to(dt), sigma=sigma)
-
-    ref, bound = _loops(run)
-    err = si.relative_error(out.reshape(ref.shape), ref)
-    print(f"host DiffPIR {prox}: rel l2 {err:.3g} bound {bound:.3g}")
-    assert err <= bound
+        assert int(sampler.last_step.iterations.max()) <= 2

@@ -16,10 +16,6 @@ reference loop's distance to its fp64 run).
 Largest errors measured on an MI355X are recorded in README.md ("Hadamard operator")."""
 
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -27,10 +23,10 @@ import torch
 
 import ddrm_ref as dr
 import hadamard_ref as hr
-import prox_ref as pr
 import stand_ins as si
-from oracle import dps_loop
-from oracle.latent_loops import pgdm_reference
+from kind_harness import (DDRM, DEBUG_SWEEP_CHILD, DPS, PROX, KindDevice, check_fused_path_and_reproduce,
+                          check_trajectory, counting_net, f32 as _f32, rounding_check as _check,
+                          run_debug_child)
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise
@@ -39,39 +35,23 @@ from samplers_amd.operators.inpainting import keep_bitmask
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
-OFFSET = 5  # sample_offset of the Philox calls
 CASE_IDS = [c[0] for c in hr.CASES]
-DPS = dict(a=0.3, k=math.sqrt(1 - 0.09), gs=400.0)
-PROX = dict(a=0.8, k=0.6, rho=0.37, a_prev=0.9, c_eps=0.3, c_xi=0.2)
-DDRM = {"big": dr.make_coefs(3.0, 0.05, 0.85, 1.0), "blend": dr.make_coefs(0.5, 0.05, 0.5, 0.5),
-        "small": dr.make_coefs(0.041, 0.05, 0.85, 1.0), "sig_y=0": dr.make_coefs(0.23, 0.0, 0.85, 1.0),
-        "sig_prev=0": dr.make_coefs(0.0, 0.05, 0.85, 1.0)}
 FORMS = [(i, f) for i in range(len(hr.CASES)) for f in hr.forms_of(i)]
 FORM_IDS = [f"{CASE_IDS[i]}-b{f[0]}-d{f[1]}" for i, f in FORMS]
 EXACT_FORMS = [(i, f) for i, f in FORMS if i in hr.EXACT]
 EXACT_IDS = [f"{CASE_IDS[i]}-b{f[0]}-d{f[1]}" for i, f in EXACT_FORMS]
 
 
-def _f32(d):
-    return {k: float(np.float32(v)) for k, v in d.items()}
+# --- a descriptor on the device -----------------------------------------------------------------------------
+class Dev(KindDevice):
+    """keep_bits, word_rank and the signs on the device and the descriptor; the prox reads y, DDRM a q."""
 
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-# --- a descriptor on the device and the raw calls ---------------------------------------------------------
-class Dev:
-    """keep_bits, word_rank and the signs on the device, the descriptor and every entry point into
-    guarded buffers."""
+    TRAITS = _hip.SP_TRAIT_UPDATE_READS_V | _hip.SP_TRAIT_DPS_WORKSPACE | _hip.SP_TRAIT_PINV
+    Q_PASSES = frozenset({"ddrm"})
 
     def __init__(self, i: int, device):
-        self.lib = _hip.load_library()
-        self.name, (self.C, self.H, self.W), keep, d = hr.case(i)
-        self.device = device
+        name, (self.C, self.H, self.W), keep, d = hr.case(i)
         self.np_, self.mp = self.H * self.W, int(keep.sum())
-        self.n, self.m = self.C * self.np_, self.C * self.mp
         self.k = self.np_.bit_length() - 1
         bits, rank = keep_bitmask(keep)
         self.bits = torch.from_numpy(bits.view(np.int64)).to(device)
@@ -79,139 +59,21 @@ class Dev:
         self.signs = None if d is None else torch.from_numpy(d).to(device)
         s = _hip.SpOp()
         s.kind, s.channels, s.height, s.width = _hip.SP_OP_HADAMARD, self.C, self.H, self.W
-        s.n, s.m, s.radius, s.factor = self.n, self.m, 0, 0
+        s.n, s.m, s.radius, s.factor = self.C * self.np_, self.C * self.mp, 0, 0
         s.keep_bits, s.word_rank = self.bits.data_ptr(), self.rank.data_ptr()
         s.taps = None if d is None else self.signs.data_ptr()
-        self.desc = s
-        assert self.lib.sp_op_traits(s) == (_hip.SP_TRAIT_UPDATE_READS_V | _hip.SP_TRAIT_DPS_WORKSPACE
-                                            | _hip.SP_TRAIT_PINV)
+        super().__init__(device, s, (self.C, self.H, self.W), (self.C, self.mp), name)
+        self.Q_ROW = self.n  # q is y itself, a row every n floats
 
-    def guarded(self, floats):
-        """`floats` NaNs between two guard bands of 16 NaNs; (whole, view)."""
-        whole = torch.full((floats + 32,), float("nan"), device=self.device)
-        return whole, whole[16:16 + floats]
-
-    def check_guards(self, whole, floats):
-        assert torch.isnan(whole[:16]).all() and torch.isnan(whole[16 + floats:]).all()
-
-    def _run(self, size_fn, batch, out_shape, call):
-        floats = int(size_fn(self.desc, batch))
+    def check_workspace(self, floats, batch):
         assert floats == batch * self.n
-        whole, work = self.guarded(floats)
-        owhole, out = self.guarded(int(np.prod(out_shape)))
-        out = out.view(out_shape)
-        _hip.check(call(out, work), "hadamard entry")
-        self.check_guards(whole, floats)
-        self.check_guards(owhole, out.numel())
-        assert torch.isfinite(out).all()
-        return out
 
-    def apply(self, x):
-        b = x.shape[0]
-        return self._run(self.lib.sp_op_workspace, b, (b, self.C, self.mp),
-                         lambda o, w: self.lib.sp_op_apply_ws(self.desc, x.data_ptr(), o.data_ptr(), b,
-                                                              w.data_ptr(), _stream()))
-
-    def adjoint(self, g):
-        b = g.shape[0]
-        return self._run(self.lib.sp_op_workspace, b, (b, self.C, self.H, self.W),
-                         lambda o, w: self.lib.sp_op_vjp_ws(self.desc, g.data_ptr(), g.data_ptr(), o.data_ptr(),
-                                                            b, w.data_ptr(), _stream()))
-
-    def pinv(self, y, transpose=0):
-        b = y.shape[0]
-        shape = (b, self.C, self.mp) if transpose else (b, self.C, self.H, self.W)
-        return self._run(self.lib.sp_op_workspace, b, shape,
-                         lambda o, w: self.lib.sp_op_pinv_ws(self.desc, y.data_ptr(), o.data_ptr(), b, transpose,
-                                                             w.data_ptr(), _stream()))
-
-    def prepare(self, y):
-        """q of the PGDM / DDRM passes: y itself, a row every n floats."""
-        rows = y.shape[0]
-        floats = int(self.lib.sp_op_workspace(self.desc, rows))
-        assert floats == rows * self.n
-        whole, q = self.guarded(floats)
-        _hip.check(self.lib.sp_pgdm_prepare(self.desc, y.data_ptr(), rows, q.data_ptr(), _stream()), "prepare")
-        self.check_guards(whole, floats)
-        q = q.view(rows, self.n)
-        assert torch.equal(q[:, :self.m], y.reshape(rows, self.m))
-        return q
-
-    def dps(self, x, eps, y, ydiv, c, sched=False):
-        b, P = x.shape[0], int(self.lib.sp_rsq_partials(self.desc))
+    def partials(self):
         hb = self.k - 12  # one partial per mid tile: the plane, or the high stage's tiles of max(2^12, 2^hb * 32)
-        assert P == self.C * (1 if hb <= 0 else self.np_ >> max(12, hb + 5))
-        pwhole, part = self.guarded(b * P)
-        coefs = _hip.SpDpsCoefs(c["a"], c["k"], c["gs"], 0.9, 0.2, 0.1, 0.05, 1e-9)
+        return self.C * (1 if hb <= 0 else self.np_ >> max(12, hb + 5))
 
-        def call(o, w):
-            if not sched:
-                return self.lib.sp_dps_residual_ws(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b,
-                                                   ydiv, coefs, o.data_ptr(), part.data_ptr(), w.data_ptr(),
-                                                   _stream())
-            recs = (_hip.SpStepRec * 2)()
-            recs[0].c, recs[0].step, recs[0].t = _hip.SpDpsCoefs(0.9, 0.4, 7.0, 0.1, 0.9, 0.6, 0.5, 1e-3), 99, 1
-            recs[1].c, recs[1].step, recs[1].t = coefs, 3, 5
-            self._sched = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(self.device)
-            self._cursor = torch.ones(1, dtype=torch.int32, device=self.device)
-            return self.lib.sp_dps_residual_sched_ws(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b,
-                                                     ydiv, self._sched.data_ptr(), self._cursor.data_ptr(),
-                                                     o.data_ptr(), part.data_ptr(), w.data_ptr(), _stream())
-
-        v = self._run(self.lib.sp_dps_workspace, b, (b, self.C, self.H, self.W), call)
-        self.check_guards(pwhole, b * P)
-        assert torch.isfinite(part).all()
-        return v, part.view(b, P)
-
-    def pgdm(self, x, eps, q, ydiv, c):
-        b = x.shape[0]
-        coefs = _hip.SpDpsCoefs(c["a"], c["k"], c["gs"], 0.9, 0.2, 0.1, 0.05, 1e-9)
-        return self._run(self.lib.sp_op_workspace, b, (b, self.C, self.H, self.W),
-                         lambda o, w: self.lib.sp_pgdm_residual_ws(self.desc, x.data_ptr(), eps.data_ptr(),
-                                                                   q.data_ptr(), b, ydiv, coefs, o.data_ptr(),
-                                                                   w.data_ptr(), _stream()))
-
-    def prox(self, x0, y, ydiv, rho):
-        b = x0.shape[0]
-        return self._run(self.lib.sp_prox_workspace, b, (b, self.C, self.H, self.W),
-                         lambda o, w: self.lib.sp_op_prox_ws(self.desc, x0.data_ptr(), y.data_ptr(), None, b, ydiv,
-                                                             rho, o.data_ptr(), w.data_ptr(), _stream()))
-
-    def _step(self, entry, size_fn, x, eps, y, q, xi, ydiv, coefs, alias, step):
-        b = x.shape[0]
-        src = x.clone() if alias else x
-
-        def call(o, w):
-            dst = src if alias else o
-            rc = entry(self.desc, src.data_ptr(), eps.data_ptr(), None if y is None else y.data_ptr(),
-                       None if q is None else q.data_ptr(), None if xi is None else xi.data_ptr(), 77, step,
-                       OFFSET, b, ydiv, coefs, dst.data_ptr(), w.data_ptr(), _stream())
-            if alias:
-                o.copy_(src)
-            return rc
-
-        return self._run(size_fn, b, (b, self.C, self.H, self.W), call)
-
-    def diffpir(self, x, eps, y, xi, ydiv, c, alias=False, step=3):
-        coefs = _hip.SpProxCoefs(c["a"], c["k"], c["rho"], c["a_prev"], c["c_eps"], c["c_xi"])
-        return self._step(self.lib.sp_diffpir_step_ws, self.lib.sp_prox_workspace, x, eps, y, None, xi, ydiv,
-                          coefs, alias, step)
-
-    def ddrm(self, x, eps, q, xi, ydiv, c, alias=False, step=3):
-        coefs = _hip.SpDdrmCoefs(*[c[k] for k in dr.KEYS])
-        return self._step(self.lib.sp_ddrm_step_ws, self.lib.sp_ddrm_workspace, x, eps, None, q, xi, ydiv,
-                          coefs, alias, step)
-
-    def randn(self, b, step=3):
-        out = torch.empty(b, self.C, self.H, self.W, device=self.device)
-        _hip.check(self.lib.sp_randn(out.data_ptr(), b, self.n, 77, step, OFFSET, _stream()), "sp_randn")
-        return out
-
-    def x0(self, x, eps, a, k):
-        out = torch.empty_like(x)
-        _hip.check(self.lib.sp_predict_x0(x.data_ptr(), eps.data_ptr(), x.numel(), a, k, out.data_ptr(),
-                                          _stream()), "sp_predict_x0")
-        return out
+    def check_q(self, q, y):
+        assert torch.equal(q[:, :self.m], y.reshape(y.shape[0], self.m))
 
 
 _DATA = {}
@@ -231,16 +93,6 @@ def _randn_case(i):
 
 def _rows(y, batch, ydiv):
     return y[: -(-batch // ydiv)]
-
-
-def _check(got, ref64, env, n_r, what, record=None):
-    """max over the elements of |got − ref64| / (n_r · 2⁻²⁴ · E) ≤ 1."""
-    ratio = float(((got.detach().cpu().double() - ref64).abs() / (n_r * hr.U24 * env)).max())
-    print(f"{what}: worst |err| / (n_r 2^-24 E) = {ratio:.3g} (n_r = {n_r})")
-    if record is not None:
-        record(f"{what}_err_over_bound", ratio, 1.0, n_r=n_r)
-    assert ratio <= 1.0, (what, ratio)
-    return ratio
 
 
 # --- exact cases: bit for bit ------------------------------------------------------------------------------
@@ -435,111 +287,20 @@ def _traj(ratio, cuda):
     return op, (keep, sg), y, InverseProblem(op, y.to(cuda), GaussianNoise(SIGMA).to(cuda))
 
 
-def _acp(dt=torch.float32):
-    return torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).to(dt)
-
-
-def _net(cuda):
-    net = si.make_samplers_amd_net("conv", 3, 0.1, device=cuda)
-    grads, inner = [], net.forward
-
-    def forward(x, t):
-        e = inner(x, t)
-        grads.append(bool(e.requires_grad) or torch.is_grad_enabled())
-        return e
-
-    net.forward = forward
-    return net, grads
-
-
-def _bound_check(out, run, what, record):
-    ref32 = run(torch.float32)
-    cond = si.relative_error(run(torch.float64), ref32)
-    bound = max(1e-4, 20 * cond)
-    err = si.relative_error(out.reshape(ref32.shape).cpu(), ref32)
-    print(f"{what}: rel l2 {err:.3g}, fp32 reference to fp64 {cond:.3g}, bound {bound:.3g}")
-    record(f"{what}_rel_l2", err, bound, fp32_to_fp64=cond)
-    assert err < bound
-
-
 @pytest.mark.parametrize("recon", [1, 2])
 @pytest.mark.parametrize("ratio", [0.25, 0.5])
 @pytest.mark.parametrize("sampler", ["dps", "pgdm", "diffpir", "ddrm"])
 def test_trajectory_matches_the_reference_loop(cuda, parity_record, sampler, ratio, recon):
-    from samplers_amd.samplers import DDRMSampler, DiffPIRSampler, DPSSampler, PGDMSampler
-
     op, (keep, sg), y, prob = _traj(ratio, cuda)
-    net, grads = _net(cuda)
-    init, steps = si.replay_noise(17, (B * recon, *SHAPE), N)
-    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
-    ts = si.leading_timesteps_ascending(N).tolist()
-    yr = y.repeat_interleave(recon, dim=0)
-    kw = dict(num_sampling_steps=N, num_reconstructions=recon, noise_fn=fn,
-              micro_batch=2 if recon == 2 else None)
-
-    def loop(dt):
-        core, S = si.EpsCore("conv", 3, 0.1).to(dt), hr.Had(SHAPE, keep, sg, dtype=dt)
-        eps_fn = lambda x, tt: core(x, tt)  # noqa: E731
-        noise = lambda i: steps[i].to(dt)  # noqa: E731
-        if sampler == "dps":
-            return dps_loop.dps_reference(eps_fn, _acp(dt), ts, S.apply, dps_loop.gaussian_log_prob(SIGMA),
-                                          yr.to(dt), init.to(dt), noise, gamma=1e-2, eta=1.0)
-        if sampler == "pgdm":
-            return pgdm_reference(eps_fn, _acp(dt), ts, S.apply, S.pinv, yr.to(dt), init.to(dt), noise,
-                                  guidance_weight=0.05, eta=1.0)
-        if sampler == "diffpir":
-            return pr.diffpir_reference(eps_fn, _acp(dt), ts, S.apply, lambda x0, yy, rho: S.prox(x0, yy, float(rho)),
-                                        yr.to(dt), init.to(dt), noise, sigma=SIGMA)
-        step = lambda x, e, yy, xi, c: S.ddrm(x, e, yy, xi, dr.round32(c) if dt == torch.float32 else c)  # noqa: E731
-        return dr.ddrm_reference(eps_fn, _acp(dt), ts, step, yr.to(dt), init.to(dt), noise, sigma_y=SIGMA)
-
-    if sampler == "dps":
-        smp = DPSSampler(net)
-        out = smp(prob, gamma=1e-2, eta=1.0, **kw)
-    elif sampler == "pgdm":
-        smp = PGDMSampler(net)
-        out = smp(prob, guidance_weight=0.05, **kw)
-    elif sampler == "diffpir":
-        smp = DiffPIRSampler(net)
-        out = smp(prob, **kw)
-        assert not smp.last_step.cg and not smp.last_step.host
-    else:
-        smp = DDRMSampler(net)
-        out = smp(prob, **kw)
-        assert smp.last_step.fused
-    if sampler in ("diffpir", "ddrm"):
-        assert smp.last_step.desc.kind == _hip.SP_OP_HADAMARD  # the HIP path ran
-    assert tuple(out.shape) == ((B, *SHAPE) if recon == 1 else (B, recon, *SHAPE))
-    if sampler in ("diffpir", "ddrm"):
-        assert len(grads) >= 2 and not any(grads)  # no network call builds an autograd graph
-    _bound_check(out, loop, f"{sampler}_r{ratio}_R{recon}", parity_record)
+    check_trajectory(cuda, parity_record, sampler, _hip.SP_OP_HADAMARD, prob, y,
+                     lambda dt: hr.Had(SHAPE, keep, sg, dtype=dt), SHAPE, N, SIGMA, recon,
+                     f"{sampler}_r{ratio}_R{recon}")
 
 
 def test_samplers_take_the_fused_path_and_reproduce(cuda):
-    from samplers_amd.samplers import DDRMSampler, DiffPIRSampler, DPSSampler, PGDMSampler
-    from samplers_amd.samplers.ddrm import FusedDDRMStep
-    from samplers_amd.samplers.diffpir import FusedDiffPIRStep
-    from samplers_amd.samplers.dps import FusedDPSStep, make_dps_step
-
     op, _, y, prob = _traj(0.25, cuda)
-    net, _ = _net(cuda)
-    rows = y.to(cuda)
-    step = FusedDDRMStep(net, prob, rows, 1)
-    assert step.fused and step.q is not None
-    for mode in ("closed_form", "auto"):
-        assert not FusedDiffPIRStep(net, prob, rows, 1, prox=mode).cg
-    assert FusedDiffPIRStep(net, prob, rows, 1, prox="cg").cg
-    for mode in ("dps", "pgdm"):  # DPS and PGDM: the fused step on the kind's descriptor, q for PGDM
-        st = make_dps_step(net, prob, rows, 1, mode=mode)
-        assert isinstance(st, FusedDPSStep) and st.desc.kind == _hip.SP_OP_HADAMARD
-        assert st.needs_v and (st.q is not None) == (mode == "pgdm")
-    for cls in (DPSSampler, PGDMSampler, DDRMSampler, DiffPIRSampler):
-        one = cls(net)(prob, num_sampling_steps=N, seed=1234)
-        assert torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1234), one) and torch.isfinite(one).all()
-        assert not torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1235), one)
-        assert torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1234, micro_batch=1), one)
-    out = DiffPIRSampler(net)(prob, num_sampling_steps=N, seed=3, prox="cg", cg_iterations=8)
-    assert torch.isfinite(out).all() and tuple(out.shape) == (B, *SHAPE)
+    net, _ = counting_net("conv", 3, 0.1, cuda)
+    check_fused_path_and_reproduce(net, prob, y.to(cuda), _hip.SP_OP_HADAMARD, N, expect_q=True)
 
 
 # --- the bounds-checked library ------------------------------------------------------------------------------
@@ -564,27 +325,10 @@ def debug_sweep(device):
         assert nv == 0, (d.name, nv, site)
 
 
-DEBUG_CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + "/tests")
-from samplers_amd import _hip
-assert _hip.load_library().sp_debug_build() == 1, "not the debug library"
-import test_hadamard_gpu as T
-_hip.debug_violations()  # clear
-T.debug_sweep(torch.device("cuda:0"))
-print("debug build: clean", flush=True)
-"""
+DEBUG_CHILD = DEBUG_SWEEP_CHILD("test_hadamard_gpu")
 
 
 def test_debug_build_has_no_violations(cuda):
     """The kernel's SP_DCHECK index invariants under the bounds-checked library, in a fresh child
     process (a process holds one library), over every shape of this file."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from kind_harness import stream as _stream
 from oracle import blur as oblur
 from oracle import closed_form, philox
 from samplers_amd import _hip
@@ -13,10 +14,6 @@ from samplers_amd.operators import (GaussianBlurOperator, IdentityOperator, Inpa
                                     get_mask_random)
 
 pytestmark = pytest.mark.gpu
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _box_mask(shape):

@@ -19,10 +19,6 @@ read from sp_rsq_partials / sp_vec_partials."""
 
 import functools
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -31,6 +27,7 @@ import torch
 import latent_ops as lo
 import sr_ops
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import blur as oblur
 from oracle import closed_form, philox
 from samplers_amd import _hip
@@ -41,7 +38,6 @@ from samplers_amd.samplers.utils.bridge_kernels import eps_step_coefficients
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 DEV = torch.device("cuda:0")
 NAN = float("nan")
 
@@ -61,10 +57,6 @@ CASE_IDS = [f"{c[0]}-{'x'.join(map(str, c[1]))}-b{c[2]}-d{c[3]}" for c in CASES]
 STRIDE = [((3, 64, 64), 400), ((1, 37, 83), 400)]
 # batch 1: one element group past 4096 blocks x 256 threads x V
 BIG_V1, BIG_V4 = 1_048_877, 4_195_504
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _call(name, *args):
@@ -785,11 +777,4 @@ def test_debug_build_has_no_violations(cuda):
     """Every entry point of this module once under the bounds-checked library (SP_DCHECK index
     invariants), in a fresh child process (a process holds one library): the six-tile scalar
     shape (1, 37, 83) at batch 3 and at batch 400 (second stride trip), inpaint and mask."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

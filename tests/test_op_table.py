@@ -9,19 +9,13 @@ import ctypes
 
 import pytest
 
+from kind_harness import make_descriptor as make
 from samplers_amd import _hip
 
 OK, EINVAL, EUNSUPPORTED = 0, -1, -3
 
 _buf = (ctypes.c_float * 64)()
 PTR = ctypes.addressof(_buf)  # a non-null dummy pointer: nothing here dereferences it
-
-
-def make(kind, n, m, c=0, h=0, w=0, radius=0, factor=0, taps=None, keep=None, rank=None):
-    d = _hip.SpOp()
-    d.kind, d.n, d.m, d.channels, d.height, d.width = kind, n, m, c, h, w
-    d.radius, d.factor, d.taps, d.keep_bits, d.word_rank = radius, factor, taps, keep, rank
-    return d
 
 
 def identity(n=12, m=None):

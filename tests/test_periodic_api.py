@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import periodic_ops as po
+from kind_harness import make_descriptor as make
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise
@@ -226,13 +227,6 @@ def test_constructor_errors():
 
 _buf = (ctypes.c_float * 64)()
 PTR = ctypes.addressof(_buf)  # a non-null dummy pointer: nothing here dereferences it
-
-
-def make(kind, n, m, c=0, h=0, w=0, radius=0, factor=0, taps=None, keep=None, rank=None):
-    d = _hip.SpOp()
-    d.kind, d.n, d.m, d.channels, d.height, d.width = kind, n, m, c, h, w
-    d.radius, d.factor, d.taps, d.keep_bits, d.word_rank = radius, factor, taps, keep, rank
-    return d
 
 
 def periodic(c=1, h=8, w=8, r=1, **kw):

@@ -20,10 +20,6 @@ fused one, bound 2.2e-2 (the fp32 oracle lies 1.1e-3 from its fp64 run: the trun
 amplifies by up to 1 / rtol)."""
 
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -32,6 +28,7 @@ import torch
 import periodic_ops as po
 import psf_ops
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import closed_form, dps_loop
 from oracle.latent_loops import pgdm_reference
 from samplers_amd import _hip
@@ -44,7 +41,6 @@ from samplers_amd.samplers.dps import FusedDPSStep, GenericDPSStep, make_dps_ste
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 
 
 def _gauss(k, sigma):
@@ -75,10 +71,6 @@ def _route(shape, r):
     """The helper's direct route up to about 2e8 multiply-adds per sample, else its FFT route
     (tests/test_periodic_api.py pins the two to each other)."""
     return "direct" if math.prod(shape) * (2 * r + 1) ** 2 <= 2e8 else "fft"
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _err(got, ref):
@@ -533,11 +525,4 @@ def test_debug_build_has_no_violations(cuda):
     """The kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh child
     process (a process holds one library): the four maps, a DPS step and a PGDM step over the
     first five cases."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

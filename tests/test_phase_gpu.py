@@ -14,10 +14,6 @@ DPS trajectories 6.3e-7 relative L2 — at the CPU fp32 figure, well below the 2
 point at imprecise twiddles."""
 
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -25,6 +21,7 @@ import torch
 
 import phase_ops
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import closed_form, dps_loop
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
@@ -35,7 +32,6 @@ from samplers_amd.samplers.dps import FusedDPSStep, GenericDPSStep, make_dps_ste
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 
 # shape, (pad_h, pad_w), batch, y_div
 CASES = [
@@ -50,10 +46,6 @@ CASES = [
     ((1, 512, 512), (256, 256), 1, 1),  # 1024 x 1024: the largest
 ]
 IDS = [f"{'x'.join(map(str, c[0]))}-p{c[1][0]}x{c[1][1]}-b{c[2]}-d{c[3]}" for c in CASES]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _err(got, ref):
@@ -417,11 +409,4 @@ print("debug build: clean", flush=True)
 def test_debug_build_has_no_violations(cuda):
     """The phase kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh
     child process (a process holds one library), over the first five table shapes."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

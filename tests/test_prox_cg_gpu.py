@@ -20,10 +20,6 @@ max(1e-4, 20 x the fp32 reference loop's distance to its fp64 run), the project'
 Measured on an MI355X: see README.md "Proximal map by conjugate gradients" (parity_record has every
 figure)."""
 
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
@@ -32,6 +28,7 @@ import prox_cg_ref as cg
 import prox_ref as pr
 import stand_ins as si
 from exact_cases import Guarded
+from kind_harness import DEBUG_SWEEP_CHILD, run_debug_child, stream as _stream
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise
@@ -40,7 +37,6 @@ from samplers_amd.operators import (GaussianBlurOperator, RadonOperator, RandomI
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 SEED, STEP, OFFSET = 11, 5, 7
 _DEV: dict = {}
 
@@ -71,10 +67,6 @@ def _dev(name, device):
     if name not in _DEV:
         _DEV[name] = Dev(name, device)
     return _DEV[name]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _work(lib, d, batch, step, device):
@@ -438,27 +430,10 @@ def debug_sweep(device):
         assert nv == 0, (name, nv, site)
 
 
-DEBUG_CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + "/tests")
-from samplers_amd import _hip
-assert _hip.load_library().sp_debug_build() == 1, "not the debug library"
-import test_prox_cg_gpu as T
-_hip.debug_violations()  # clear
-T.debug_sweep(torch.device("cuda:0"))
-print("debug build: clean", flush=True)
-"""
+DEBUG_CHILD = DEBUG_SWEEP_CHILD("test_prox_cg_gpu")
 
 
 def test_debug_build_has_no_violations(cuda):
     """The new kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh
     child process (a process holds one library), over every shape of this file."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

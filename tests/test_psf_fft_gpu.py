@@ -18,11 +18,7 @@ pixel solve 8.1e-7, 1.7e-6 against the direct SP_OP_PSF kernel at R = 30 — at 
 figure."""
 
 import math
-import os
-import subprocess
-import sys
 import types
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -31,6 +27,7 @@ import torch
 import psf_fft_ops
 import psf_ops
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import closed_form, dps_loop
 from oracle.latent_loops import psld_reference
 from samplers_amd import _hip
@@ -42,7 +39,6 @@ from samplers_amd.samplers.dps import FusedDPSStep, GenericDPSStep, make_dps_ste
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 
 # shape, R, batch, y_div, padding modes
 ALL = ("reflect", "circular", "zeros")
@@ -74,10 +70,6 @@ def _kernel(r, kind):
 def _route(shape, r):
     """The helper's direct route up to about 2e8 multiply-adds per sample, else its FFT route."""
     return "direct" if math.prod(shape) * (2 * r + 1) ** 2 <= 2e8 else "fft"
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _err(got, ref):
@@ -501,11 +493,4 @@ def test_debug_build_has_no_violations(cuda):
     """The kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh child
     process (a process holds one library): the maps and a DPS step over the first five table
     shapes in the three modes."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -9,11 +9,7 @@ pixel-optimisation iterate.  The same pass-1 arithmetic in fp32 torch on the CPU
 8.6e-7 x max|v| of fp64 at R = 30 on 3x64x64 (1e-7 at R = 1), so 2e-5 leaves > 20x headroom."""
 
 import math
-import os
-import subprocess
-import sys
 import types
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -21,6 +17,7 @@ import torch
 
 import psf_ops
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import closed_form, dps_loop
 from oracle.latent_loops import psld_reference
 from samplers_amd import _hip
@@ -31,7 +28,6 @@ from samplers_amd.samplers import DPSSampler
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 
 
 def gappy_kernel(radius: int) -> torch.Tensor:
@@ -70,10 +66,6 @@ MULTI_TILE = {(1, 70, 132): 9, (2, 40, 70): 8}  # sp_rsq_partials of the cases w
 
 def _kernel(r, kind, seed=0):
     return gappy_kernel(r) if kind == "gappy" else psf_ops.random_sparse_kernel(r, seed=100 * r + seed)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _close(got, ref, what, record=None):
@@ -438,11 +430,4 @@ def test_debug_build_has_no_violations(cuda):
     """The PSF kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh
     child process (a process holds one library): a float4-store case, the element-wise
     (2, 7, 10) case and one with several tiles."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -39,11 +39,7 @@ largest shapes); |r|^2 4.7e-7; DPS 2.3e-6 (Gaussian), 2.5e-7 (Poisson); PSLD 4.6
 """
 
 import math
-import os
-import subprocess
-import sys
 import types
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -52,6 +48,7 @@ import torch
 import exact_cases as ec
 import radon_ref as rr
 import stand_ins as si
+from kind_harness import run_debug_child
 from oracle import dps_loop
 from oracle.latent_loops import psld_reference
 from samplers_amd import _hip
@@ -62,7 +59,6 @@ from samplers_amd.samplers import DPSSampler
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 NAMES = list(rr.CASES)
 
 
@@ -456,11 +452,4 @@ print("debug build: clean", flush=True)
 def test_debug_build_has_no_violations(cuda):
     """The projector kernels' SP_DCHECK index invariants under the bounds-checked library, in a
     fresh child process (a process holds one library), over every shape of the kernel cases."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

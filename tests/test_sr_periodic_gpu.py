@@ -20,10 +20,6 @@ SP_OP_PSF_PERIODIC; trajectories bicubic / Gaussian: DPS 3.3e-7 / 3.0e-7, DiffPI
 PSLD 3.7e-7 / 4.5e-7, PGDM 6.9e-4 / 9.9e-3 under 2.5e-2 / 2.2e-1."""
 
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
@@ -32,6 +28,7 @@ import exact_cases as ec
 import prox_ref as pr
 import sr_periodic_ops as so
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import dps_loop
 from oracle.latent_loops import pgdm_reference, psld_reference
 from samplers_amd import _hip
@@ -44,7 +41,6 @@ from samplers_amd.samplers import DPSSampler
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 BOUND = 2e-5
 SEED, STEP, OFFSET = 1234, 5, 3
 
@@ -70,10 +66,6 @@ CASES = [
 IDS = [f"{'x'.join(map(str, c[0]))}-s{c[1]}-{i}" for i, c in enumerate(CASES)]
 BATCHES = [(3, 3), (4, 2)]
 BIG = len(CASES) - 1
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _batches(i, batch, ydiv):
@@ -614,11 +606,4 @@ print("debug build: clean", flush=True)
 def test_debug_build_has_no_violations(cuda):
     """The kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh child
     process (a process holds one library): every entry point over the ten small cases."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -8,11 +8,7 @@ relative L2 for the DPS / PSLD trajectories, max(1e-4, 20 x the oracle's own fp3
 distance) for PGDM (test_latent_gpu.py), 1e-5 for graph replay (test_graph_gpu.py)."""
 
 import math
-import os
-import subprocess
-import sys
 import types
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -20,6 +16,7 @@ import torch
 
 import sr_ops
 import stand_ins as si
+from kind_harness import run_debug_child, stream as _stream
 from oracle import closed_form, dps_loop
 from oracle.latent_loops import pgdm_reference, psld_reference
 from samplers_amd import _hip
@@ -30,7 +27,6 @@ from samplers_amd.samplers import DPSSampler
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 
 # shape, factor, batch, y_div
 CASES = [
@@ -43,10 +39,6 @@ CASES = [
     ((3, 64, 128), 4, 2, 1),                       # more than one tile: fixed-order partial sum
 ]
 IDS = [f"{'x'.join(map(str, c[0]))}-s{c[1]}-b{c[2]}-d{c[3]}" for c in CASES]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _replicate(y, s):
@@ -425,11 +417,4 @@ print("debug build: clean", flush=True)
 def test_debug_build_has_no_violations(cuda):
     """The SR kernels' SP_DCHECK index invariants under the bounds-checked library, in a fresh
     child process (a process holds one library), on the lane-pair and the scalar path."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

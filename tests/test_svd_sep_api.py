@@ -9,14 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-import ddrm_ref as dr
-import stand_ins as si
 import svd_sep_ref as sr
+from kind_harness import host_ddrm_check, host_diffpir_check, host_pgdm_check, host_refusals
 from samplers_amd import _hip
-from samplers_amd.inverse_problem import InverseProblem
-from samplers_amd.noise import GaussianNoise
 from samplers_amd.operators import SeparableSVDOperator, SVDOperator
-from samplers_amd.samplers import DDRMSampler
 
 KIND, EINVAL, EUNSUPPORTED = 11, -1, -3
 _buf = (ctypes.c_float * 64)()
@@ -194,45 +190,6 @@ def test_descriptor_and_interface(lib):
     assert ddrm_descriptor(op).kind == prox_descriptor(op).kind == cg_descriptor(op).kind == KIND
 
 
-@pytest.mark.parametrize("recon", [1, 2])
-def test_host_ddrm_sampler_is_the_plain_loop(recon):
-    shape, N, B, sigma = (1, 12, 10), 6, 2, 0.1
-    op = SeparableSVDOperator.from_taps(shape, sr._gauss(3, 0.8), sr._gauss(5, 1.2))
-    t = sr.Tables.from_flat(op.tables, 12, 10, 12, 10)
-    assert 0.1 <= t.kept_share() <= 0.9
-    g = torch.Generator().manual_seed(4)
-    y = torch.randn(B, *shape, generator=g)
-    net = si.make_samplers_amd_net("conv", 1, 0.1)
-    calls, inner = [], net.forward
-
-    def forward(x, tt):
-        calls.append(torch.is_grad_enabled())
-        return inner(x, tt)
-
-    net.forward = forward
-    init, steps = si.replay_noise(21, (B * recon, *shape), N)
-    fn = lambda kind, i, sh: init.clone() if kind == "init" else steps[i]  # noqa: E731
-    out = DDRMSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=N,
-                           num_reconstructions=recon, noise_fn=fn, micro_batch=2 if recon == 2 else None)
-    assert tuple(out.shape) == ((B, *shape) if recon == 1 else (B, recon, *shape))
-    assert len(calls) >= N - 1 and not any(calls)  # every network call under no_grad
-    core, S = si.EpsCore("conv", 1, 0.1).double(), sr.Sep(t)
-    acp = torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).double()
-    ref = dr.ddrm_reference(lambda x, tt: core(x, tt), acp, si.leading_timesteps_ascending(N).tolist(),
-                            lambda x, e, yy, xi, c: S.ddrm(x, e, yy, xi, c),
-                            y.repeat_interleave(recon, dim=0).double(), init.double(),
-                            lambda i: steps[i].double(), sigma_y=sigma)
-    err = si.relative_error(out.reshape(ref.shape), ref)
-    print(f"host DDRM R={recon}: rel l2 {err:.3g}")
-    assert err <= 1e-4  # fp32 plain torch against the fp64 loop over N - 2 steps
-    # DPS has no host form: its fused step needs a device
-    from samplers_amd.samplers import DPSSampler
-    with pytest.raises(_hip.HipLibraryError):
-        DPSSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=4)
-    with pytest.raises((ValueError, _hip.HipLibraryError)):  # the host path draws no Philox noise
-        DDRMSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=4, seed=1)
-
-
 def _host_problem():
     shape, sigma = (1, 12, 10), 0.1
     op = SeparableSVDOperator.from_taps(shape, sr._gauss(3, 0.8), sr._gauss(5, 1.2))
@@ -241,79 +198,36 @@ def _host_problem():
     return shape, sigma, op, t, y
 
 
-def _loops(run):
-    """(fp32 reference loop, max(1e-4, 20 x its distance to the fp64 run))."""
-    ref32 = run(torch.float32)
-    return ref32, max(1e-4, 20 * si.relative_error(run(torch.float64), ref32))
+@pytest.mark.parametrize("recon", [1, 2])
+def test_host_ddrm_sampler_is_the_plain_loop(recon):
+    shape, sigma, op, t, y = _host_problem()
+    assert 0.1 <= t.kept_share() <= 0.9
+    host_ddrm_check(op, sr.Sep(t), y, shape, sigma, recon)
+    host_refusals(op, y, shape, sigma)
 
 
 @pytest.mark.parametrize("recon", [1, 2])
 def test_host_pgdm_sampler_is_the_plain_loop(recon):
-    from oracle.latent_loops import pgdm_reference
-    from samplers_amd.samplers import PGDMSampler
+    shape, sigma, op, t, y = _host_problem()
+    host_pgdm_check(op, lambda dt: sr.Sep(t, dtype=dt), y, shape, sigma, recon)
 
-    (shape, sigma, op, t, y), N, B = _host_problem(), 6, 2
-    net = si.make_samplers_amd_net("conv", 1, 0.1)
-    init, steps = si.replay_noise(21, (B * recon, *shape), N)
-    fn = lambda kind, i, sh: init.clone() if kind == "init" else steps[i]  # noqa: E731
-    out = PGDMSampler(net)(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=N,
-                           num_reconstructions=recon, guidance_weight=0.05, noise_fn=fn,
-                           micro_batch=2 if recon == 2 else None)
-    assert tuple(out.shape) == ((B, *shape) if recon == 1 else (B, recon, *shape))
 
-    def run(dt):
-        core, S = si.EpsCore("conv", 1, 0.1).to(dt), sr.Sep(t, dtype=dt)
-        acp = torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).to(dt)
-        return pgdm_reference(lambda x, tt: core(x, tt), acp, si.leading_timesteps_ascending(N).tolist(),
-                              S.apply, S.pinv, y.repeat_interleave(recon, dim=0).to(dt), init.to(dt),
-                              lambda i: steps[i].to(dt), guidance_weight=0.05, eta=1.0)
+def _cg_sep(t, dt):
+    """Sep whose data step is the plain CGLS recurrence (K = 16, tol 1e-4) on the dense matrix."""
+    import prox_cg_ref as cg
 
-    ref, bound = _loops(run)
-    err = si.relative_error(out.reshape(ref.shape), ref)
-    print(f"host PGDM R={recon}: rel l2 {err:.3g} bound {bound:.3g}")
-    assert err <= bound
+    S, A = sr.Sep(t, dtype=dt), torch.from_numpy(sr.Dense(t).A)
+
+    def prox(x0, yy, rho):
+        z, _ = cg.cgls(A, x0.reshape(len(x0), -1), yy.reshape(len(x0), -1), rho, 16, 1e-4, dtype=dt)
+        return z.reshape(x0.shape)
+
+    S.prox = prox
+    return S
 
 
 @pytest.mark.parametrize("prox", ["cg", "closed_form"])
 def test_host_diffpir_sampler_is_the_plain_loop(prox):
-    import prox_cg_ref as cg
-    import prox_ref as pr
-    from samplers_amd.samplers import DiffPIRSampler
-
-    (shape, sigma, op, t, y), N, B, K, tol = _host_problem(), 6, 2, 16, 1e-4
-    A = torch.from_numpy(sr.Dense(t).A)
-    net = si.make_samplers_amd_net("conv", 1, 0.1)
-    calls, inner = [], net.forward
-
-    def forward(x, tt):
-        calls.append(torch.is_grad_enabled())
-        return inner(x, tt)
-
-    net.forward = forward
-    init, steps = si.replay_noise(21, (B, *shape), N)
-    fn = lambda kind, i, sh: init.clone() if kind == "init" else steps[i]  # noqa: E731
-    sampler = DiffPIRSampler(net)
-    out = sampler(InverseProblem(op, y, GaussianNoise(sigma)), num_sampling_steps=N, noise_fn=fn, prox=prox,
-                  cg_iterations=K, cg_tol=tol)
-    assert len(calls) >= N - 1 and not any(calls)  # every network call under no_grad
-    if prox == "cg":
-        assert tuple(sampler.last_step.iterations.shape) == (N - 2, B)
-
-    def run(dt):
-        core, S = si.EpsCore("conv", 1, 0.1).to(dt), sr.Sep(t, dtype=dt)
-        acp = torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).to(dt)
-
-        def data_step(x0, yy, rho):
-            if prox == "closed_form":
-                return S.prox(x0, yy, float(rho))
-            z, _ = cg.cgls(A, x0.reshape(B, -1), yy.reshape(B, -1), float(rho), K, tol, dtype=dt)
-            return z.reshape(x0.shape)
-
-        return pr.diffpir_reference(lambda x, tt: core(x, tt), acp, si.leading_timesteps_ascending(N).tolist(),
-                                    S.apply, data_step, y.to(dt), init.to(dt), lambda i: steps[i].to(dt),
-                                    sigma=sigma)
-
-    ref, bound = _loops(run)
-    err = si.relative_error(out.reshape(ref.shape), ref)
-    print(f"host DiffPIR {prox}: rel l2 {err:.3g} bound {bound:.3g}")
-    assert err <= bound
+    shape, sigma, op, t, y = _host_problem()
+    make_S = (lambda dt: _cg_sep(t, dt)) if prox == "cg" else (lambda dt: sr.Sep(t, dtype=dt))
+    host_diffpir_check(op, make_S, y, shape, sigma, prox, tol=1e-4)

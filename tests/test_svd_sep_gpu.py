@@ -12,22 +12,15 @@ reference loop's distance to its fp64 run).
 
 Largest errors measured on an MI355X are recorded in README.md ("Separable-SVD operator")."""
 
-import math
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
 import ddrm_ref as dr
-import prox_ref as pr
 import stand_ins as si
 import svd_sep_ref as sr
-from oracle import dps_loop
-from oracle.latent_loops import pgdm_reference
+from kind_harness import (DDRM, DEBUG_SWEEP_CHILD, DPS, PROX, KindDevice, check_fused_path_and_reproduce,
+                          check_trajectory, counting_net, f32 as _f32, run_debug_child)
 from samplers_amd import _hip
 from samplers_amd.inverse_problem import InverseProblem
 from samplers_amd.noise import GaussianNoise
@@ -36,176 +29,38 @@ from samplers_amd.operators.base import _host_prox_cg
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 FLOOR = 2e-5
-OFFSET = 5  # sample_offset of the Philox calls
 FACTOR_IDS = [c[0] for c in sr.FACTOR_CASES]
 EXACT_IDS = [c[0] for c in sr.EXACT_CASES]
 FORM_IDS = [f"b{b}-d{d}" for b, d in sr.BATCH_FORMS]
-DPS = dict(a=0.3, k=math.sqrt(1 - 0.09), gs=400.0)
-PROX = dict(a=0.8, k=0.6, rho=0.37, a_prev=0.9, c_eps=0.3, c_xi=0.2)
-DDRM = {"big": dr.make_coefs(3.0, 0.05, 0.85, 1.0), "blend": dr.make_coefs(0.5, 0.05, 0.5, 0.5),
-        "small": dr.make_coefs(0.041, 0.05, 0.85, 1.0), "sig_y=0": dr.make_coefs(0.23, 0.0, 0.85, 1.0),
-        "sig_prev=0": dr.make_coefs(0.0, 0.05, 0.85, 1.0)}
 
 
-def _f32(d):
-    return {k: float(np.float32(v)) for k, v in d.items()}
+# --- a descriptor on the device -----------------------------------------------------------------------------
+class Dev(KindDevice):
+    """The tables on the device and the descriptor; the prox and DDRM each read a prepared q."""
 
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-# --- a descriptor on the device and the raw calls ---------------------------------------------------------
-class Dev:
-    """The tables on the device, the descriptor and every entry point into guarded buffers."""
+    TRAITS = _hip.SP_TRAIT_UPDATE_READS_V | _hip.SP_TRAIT_DPS_WORKSPACE | _hip.SP_TRAIT_PINV
+    Q_PASSES = frozenset({"prox", "ddrm"})
 
     def __init__(self, t: sr.Tables, C: int, device):
-        self.lib = _hip.load_library()
-        self.t, self.C, self.device = t, C, device
+        self.t, self.C = t, C
         self.H, self.W, self.Hy, self.Wy = t.dims
-        self.n, self.m = C * self.H * self.W, C * self.Hy * self.Wy
         self.tables = t.flat32().to(device)
         d = _hip.SpOp()
         d.kind, d.channels, d.height, d.width = _hip.SP_OP_SVD_SEPARABLE, C, self.H, self.W
-        d.n, d.m, d.radius, d.factor, d.taps = self.n, self.m, self.Hy, self.Wy, self.tables.data_ptr()
-        self.desc = d
-        assert self.lib.sp_op_traits(d) == (_hip.SP_TRAIT_UPDATE_READS_V | _hip.SP_TRAIT_DPS_WORKSPACE
-                                            | _hip.SP_TRAIT_PINV)
+        d.n, d.m, d.radius, d.factor = C * self.H * self.W, C * self.Hy * self.Wy, self.Hy, self.Wy
+        d.taps = self.tables.data_ptr()
+        super().__init__(device, d, (C, self.H, self.W), (C, self.Hy, self.Wy), "svd_separable")
+        self.Q_ROW = 2 * self.n  # P T_y(y) for PGDM / DDRM, S T_y(y) for the prox: m floats of it used
 
-    def guarded(self, floats):
-        """`floats` NaNs between two guard bands of 16 NaNs; (whole, view)."""
-        whole = torch.full((floats + 32,), float("nan"), device=self.device)
-        return whole, whole[16:16 + floats]
-
-    def check_guards(self, whole, floats):
-        assert torch.isnan(whole[:16]).all() and torch.isnan(whole[16 + floats:]).all()
-
-    def _run(self, size_fn, batch, out_shape, call):
-        floats = int(size_fn(self.desc, batch))
+    def check_workspace(self, floats, batch):
         assert floats > 0
-        whole, work = self.guarded(floats)
-        out = torch.full(out_shape, float("nan"), device=self.device)
-        _hip.check(call(out, work), "svd_separable entry")
-        self.check_guards(whole, floats)
-        assert torch.isfinite(out).all()
-        return out
 
-    def apply(self, x):
-        b = x.shape[0]
-        return self._run(self.lib.sp_op_workspace, b, (b, self.C, self.Hy, self.Wy),
-                         lambda o, w: self.lib.sp_op_apply_ws(self.desc, x.data_ptr(), o.data_ptr(), b,
-                                                              w.data_ptr(), _stream()))
+    def partials(self):
+        return self.C * -(-self.Hy // 64) * -(-self.Wy // 64)
 
-    def adjoint(self, g):
-        b = g.shape[0]
-        return self._run(self.lib.sp_op_workspace, b, (b, self.C, self.H, self.W),
-                         lambda o, w: self.lib.sp_op_vjp_ws(self.desc, g.data_ptr(), g.data_ptr(), o.data_ptr(),
-                                                            b, w.data_ptr(), _stream()))
-
-    def pinv(self, y, transpose=0):
-        b = y.shape[0]
-        shape = (b, self.C, self.Hy, self.Wy) if transpose else (b, self.C, self.H, self.W)
-        return self._run(self.lib.sp_op_workspace, b, shape,
-                         lambda o, w: self.lib.sp_op_pinv_ws(self.desc, y.data_ptr(), o.data_ptr(), b, transpose,
-                                                             w.data_ptr(), _stream()))
-
-    def prepare(self, y, prox=False):
-        """q of the PGDM / DDRM passes (P T_y(y)) or of the prox (S T_y(y)): (rows, 2 n), m used."""
-        rows = y.shape[0]
-        size = self.lib.sp_prox_prepare_size if prox else self.lib.sp_op_workspace
-        floats = int(size(self.desc, rows))
-        assert floats == 2 * rows * self.n
-        whole, q = self.guarded(floats)
-        fn = self.lib.sp_prox_prepare if prox else self.lib.sp_pgdm_prepare
-        _hip.check(fn(self.desc, y.data_ptr(), rows, q.data_ptr(), _stream()), "prepare")
-        self.check_guards(whole, floats)
-        q = q.view(rows, 2 * self.n)
+    def check_q(self, q, y):
         assert torch.isfinite(q[:, :self.m]).all()
-        return q
-
-    def dps(self, x, eps, y, ydiv, c, sched=False):
-        b, P = x.shape[0], int(self.lib.sp_rsq_partials(self.desc))
-        assert P == self.C * -(-self.Hy // 64) * -(-self.Wy // 64)
-        pwhole, part = self.guarded(b * P)
-        coefs = _hip.SpDpsCoefs(c["a"], c["k"], c["gs"], 0.9, 0.2, 0.1, 0.05, 1e-9)
-
-        def call(o, w):
-            if not sched:
-                return self.lib.sp_dps_residual_ws(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b,
-                                                   ydiv, coefs, o.data_ptr(), part.data_ptr(), w.data_ptr(),
-                                                   _stream())
-            recs = (_hip.SpStepRec * 2)()
-            recs[0].c, recs[0].step, recs[0].t = _hip.SpDpsCoefs(0.9, 0.4, 7.0, 0.1, 0.9, 0.6, 0.5, 1e-3), 99, 1
-            recs[1].c, recs[1].step, recs[1].t = coefs, 3, 5
-            self._sched = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(self.device)
-            self._cursor = torch.ones(1, dtype=torch.int32, device=self.device)
-            return self.lib.sp_dps_residual_sched_ws(self.desc, x.data_ptr(), eps.data_ptr(), y.data_ptr(), b,
-                                                     ydiv, self._sched.data_ptr(), self._cursor.data_ptr(),
-                                                     o.data_ptr(), part.data_ptr(), w.data_ptr(), _stream())
-
-        v = self._run(self.lib.sp_dps_workspace, b, (b, self.C, self.H, self.W), call)
-        self.check_guards(pwhole, b * P)
-        assert torch.isfinite(part).all()
-        return v, part.view(b, P)
-
-    def pgdm(self, x, eps, q, ydiv, c):
-        b = x.shape[0]
-        coefs = _hip.SpDpsCoefs(c["a"], c["k"], c["gs"], 0.9, 0.2, 0.1, 0.05, 1e-9)
-        return self._run(self.lib.sp_op_workspace, b, (b, self.C, self.H, self.W),
-                         lambda o, w: self.lib.sp_pgdm_residual_ws(self.desc, x.data_ptr(), eps.data_ptr(),
-                                                                   q.data_ptr(), b, ydiv, coefs, o.data_ptr(),
-                                                                   w.data_ptr(), _stream()))
-
-    def prox(self, x0, q, ydiv, rho):
-        b = x0.shape[0]
-        return self._run(self.lib.sp_prox_workspace, b, (b, self.C, self.H, self.W),
-                         lambda o, w: self.lib.sp_op_prox_ws(self.desc, x0.data_ptr(), None, q.data_ptr(), b, ydiv,
-                                                             rho, o.data_ptr(), w.data_ptr(), _stream()))
-
-    def diffpir(self, x, eps, q, xi, ydiv, c, alias=False, step=3):
-        b = x.shape[0]
-        coefs = _hip.SpProxCoefs(c["a"], c["k"], c["rho"], c["a_prev"], c["c_eps"], c["c_xi"])
-        src = x.clone() if alias else x
-
-        def call(o, w):
-            dst = src if alias else o
-            rc = self.lib.sp_diffpir_step_ws(self.desc, src.data_ptr(), eps.data_ptr(), None, q.data_ptr(),
-                                             None if xi is None else xi.data_ptr(), 77, step, OFFSET, b, ydiv,
-                                             coefs, dst.data_ptr(), w.data_ptr(), _stream())
-            if alias:
-                o.copy_(src)
-            return rc
-
-        return self._run(self.lib.sp_prox_workspace, b, (b, self.C, self.H, self.W), call)
-
-    def ddrm(self, x, eps, q, xi, ydiv, c, alias=False, step=3):
-        b = x.shape[0]
-        coefs = _hip.SpDdrmCoefs(*[c[k] for k in dr.KEYS])
-        src = x.clone() if alias else x
-
-        def call(o, w):
-            dst = src if alias else o
-            rc = self.lib.sp_ddrm_step_ws(self.desc, src.data_ptr(), eps.data_ptr(), None, q.data_ptr(),
-                                          None if xi is None else xi.data_ptr(), 77, step, OFFSET, b, ydiv,
-                                          coefs, dst.data_ptr(), w.data_ptr(), _stream())
-            if alias:
-                o.copy_(src)
-            return rc
-
-        return self._run(self.lib.sp_ddrm_workspace, b, (b, self.C, self.H, self.W), call)
-
-    def randn(self, b, step=3):
-        out = torch.empty(b, self.C, self.H, self.W, device=self.device)
-        _hip.check(self.lib.sp_randn(out.data_ptr(), b, self.n, 77, step, OFFSET, _stream()), "sp_randn")
-        return out
-
-    def x0(self, x, eps, a, k):
-        out = torch.empty_like(x)
-        _hip.check(self.lib.sp_predict_x0(x.data_ptr(), eps.data_ptr(), x.numel(), a, k, out.data_ptr(),
-                                          _stream()), "sp_predict_x0")
-        return out
 
 
 _FACTOR = {}
@@ -457,101 +312,20 @@ def _traj(name, cuda):
     return op, t, y, InverseProblem(op, y.to(cuda), GaussianNoise(SIGMA).to(cuda))
 
 
-def _acp(dt=torch.float32):
-    return torch.cat([torch.ones(1), si.ddpm_alphas_cumprod()]).clip(1e-6, 1).to(dt)
-
-
-def _net(cuda):
-    net = si.make_samplers_amd_net("conv", 3, 0.1, device=cuda)
-    grads, inner = [], net.forward
-
-    def forward(x, t):
-        e = inner(x, t)
-        grads.append(bool(e.requires_grad) or torch.is_grad_enabled())
-        return e
-
-    net.forward = forward
-    return net, grads
-
-
-def _bound_check(out, run, what, record):
-    ref32 = run(torch.float32)
-    cond = si.relative_error(run(torch.float64), ref32)
-    bound = max(1e-4, 20 * cond)
-    err = si.relative_error(out.reshape(ref32.shape).cpu(), ref32)
-    print(f"{what}: rel l2 {err:.3g}, fp32 reference to fp64 {cond:.3g}, bound {bound:.3g}")
-    record(f"{what}_rel_l2", err, bound, fp32_to_fp64=cond)
-    assert err < bound
-
-
 @pytest.mark.parametrize("recon", [1, 2])
 @pytest.mark.parametrize("name", ["blur", "sr"])
 @pytest.mark.parametrize("sampler", ["dps", "pgdm", "diffpir", "ddrm"])
 def test_trajectory_matches_the_reference_loop(cuda, parity_record, sampler, name, recon):
-    from samplers_amd.samplers import DDRMSampler, DiffPIRSampler, DPSSampler, PGDMSampler
-
     op, t, y, prob = _traj(name, cuda)
-    net, grads = _net(cuda)
-    init, steps = si.replay_noise(17, (B * recon, *SHAPE), N)
-    fn = lambda kind, i, sh: (init if kind == "init" else steps[i]).to(cuda)  # noqa: E731
-    ts = si.leading_timesteps_ascending(N).tolist()
-    yr = y.repeat_interleave(recon, dim=0)
-    kw = dict(num_sampling_steps=N, num_reconstructions=recon, noise_fn=fn,
-              micro_batch=2 if recon == 2 else None)
-
-    def loop(dt):
-        core, S = si.EpsCore("conv", 3, 0.1).to(dt), sr.Sep(t, dtype=dt)
-        eps_fn = lambda x, tt: core(x, tt)  # noqa: E731
-        noise = lambda i: steps[i].to(dt)  # noqa: E731
-        if sampler == "dps":
-            return dps_loop.dps_reference(eps_fn, _acp(dt), ts, S.apply, dps_loop.gaussian_log_prob(SIGMA),
-                                          yr.to(dt), init.to(dt), noise, gamma=1e-2, eta=1.0)
-        if sampler == "pgdm":
-            return pgdm_reference(eps_fn, _acp(dt), ts, S.apply, S.pinv, yr.to(dt), init.to(dt), noise,
-                                  guidance_weight=0.05, eta=1.0)
-        if sampler == "diffpir":
-            return pr.diffpir_reference(eps_fn, _acp(dt), ts, S.apply, lambda x0, yy, rho: S.prox(x0, yy, float(rho)),
-                                        yr.to(dt), init.to(dt), noise, sigma=SIGMA)
-        step = lambda x, e, yy, xi, c: S.ddrm(x, e, yy, xi, dr.round32(c) if dt == torch.float32 else c)  # noqa: E731
-        return dr.ddrm_reference(eps_fn, _acp(dt), ts, step, yr.to(dt), init.to(dt), noise, sigma_y=SIGMA)
-
-    if sampler == "dps":
-        out = DPSSampler(net)(prob, gamma=1e-2, eta=1.0, **kw)
-    elif sampler == "pgdm":
-        out = PGDMSampler(net)(prob, guidance_weight=0.05, **kw)
-    elif sampler == "diffpir":
-        out = DiffPIRSampler(net)(prob, **kw)
-    else:
-        out = DDRMSampler(net)(prob, **kw)
-    assert tuple(out.shape) == ((B, *SHAPE) if recon == 1 else (B, recon, *SHAPE))
-    if sampler in ("diffpir", "ddrm"):
-        assert len(grads) >= 2 and not any(grads)  # no network call builds an autograd graph
-    _bound_check(out, loop, f"{sampler}_{name}_R{recon}", parity_record)
+    check_trajectory(cuda, parity_record, sampler, _hip.SP_OP_SVD_SEPARABLE, prob, y,
+                     lambda dt: sr.Sep(t, dtype=dt), SHAPE, N, SIGMA, recon, f"{sampler}_{name}_R{recon}")
 
 
 def test_samplers_take_the_fused_path_and_reproduce(cuda):
-    from samplers_amd.samplers import DDRMSampler, DiffPIRSampler
-    from samplers_amd.samplers.ddrm import FusedDDRMStep
-    from samplers_amd.samplers.diffpir import FusedDiffPIRStep
-
     op, t, y, prob = _traj("blur", cuda)
-    net, _ = _net(cuda)
-    rows = y.to(cuda)
-    step = FusedDDRMStep(net, prob, rows, 1)
-    assert step.fused and step.q is not None
-    for mode in ("closed_form", "auto"):
-        st = FusedDiffPIRStep(net, prob, rows, 1, prox=mode)
-        assert not st.cg and st.q is not None
-    assert FusedDiffPIRStep(net, prob, rows, 1, prox="cg").cg
-    for cls in (DDRMSampler, DiffPIRSampler):
-        one = cls(net)(prob, num_sampling_steps=N, seed=1234)
-        assert torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1234), one) and torch.isfinite(one).all()
-        assert not torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1235), one)
-        assert torch.equal(cls(net)(prob, num_sampling_steps=N, seed=1234, micro_batch=1), one)
-    # conjugate gradients run through the kind's apply_ws / vjp_ws (the maps' agreement with the
-    # closed form is test_conjugate_gradients_reach_the_closed_form's)
-    out = DiffPIRSampler(net)(prob, num_sampling_steps=N, seed=3, prox="cg", cg_iterations=8)
-    assert torch.isfinite(out).all() and tuple(out.shape) == (B, *SHAPE)
+    net, _ = counting_net("conv", 3, 0.1, cuda)
+    steps = check_fused_path_and_reproduce(net, prob, y.to(cuda), _hip.SP_OP_SVD_SEPARABLE, N, expect_q=True)
+    assert steps["closed_form"].q is not None and steps["auto"].q is not None  # S T_y(y), prepared once
 
 
 # --- the bounds-checked library ------------------------------------------------------------------------------
@@ -580,27 +354,10 @@ def debug_sweep(device):
         assert nv == 0, (name, nv, site)
 
 
-DEBUG_CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + "/tests")
-from samplers_amd import _hip
-assert _hip.load_library().sp_debug_build() == 1, "not the debug library"
-import test_svd_sep_gpu as T
-_hip.debug_violations()  # clear
-T.debug_sweep(torch.device("cuda:0"))
-print("debug build: clean", flush=True)
-"""
+DEBUG_CHILD = DEBUG_SWEEP_CHILD("test_svd_sep_gpu")
 
 
 def test_debug_build_has_no_violations(cuda):
     """The kernel's SP_DCHECK index invariants under the bounds-checked library, in a fresh child
     process (a process holds one library), over every shape of this file."""
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)

@@ -35,20 +35,16 @@ tests/rows_ref.py in brackets); ``parity_record`` holds every one:
 from __future__ import annotations
 
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
 
 import gn_ref
 import rows_ref as rr
+from kind_harness import run_debug_child
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 SP_OK, SP_EINVAL = 0, -1
 ROWS, TAIL = rr.ROWS, rr.TAIL
 F32, BF16 = torch.float32, torch.bfloat16
@@ -675,13 +671,4 @@ def test_debug_build_has_no_violations(cuda):
     """The row kernels' SP_DCHECK width invariants (the row fits the instantiation's registers)
     under the bounds-checked library, in a fresh child process (a process holds one library), at
     the widths on either side of each 64-vector boundary."""
-    from samplers_amd import _hip
-
-    if not _hip.DEBUG_LIB_PATH.exists():
-        pytest.fail(f"{_hip.DEBUG_LIB_PATH} missing: run `make` (builds the debug library too)")
-    env = dict(os.environ, SAMPLERS_HIP_LIB=str(_hip.DEBUG_LIB_PATH))
-    out = subprocess.run([sys.executable, "-c", DEBUG_CHILD, str(ROOT)], env=env,
-                         capture_output=True, text=True, timeout=240)
-    print(out.stdout[-4000:], out.stderr[-4000:])
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "debug build: clean" in out.stdout
+    run_debug_child(DEBUG_CHILD)
